@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the DeepCLR forward hot path on MI355X: scan-pairs/s (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,6 +15,9 @@ exchange is an RCCL all-gather of the pose outputs.
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (one fresh child process
 per GPU, before this process has touched the GPU) and relays rank 0's JSON line. Rank 0 prints ONE JSON line.
 The CPU oracle is used only for the `cpu_baseline` leg and the pose check -- never inside the timed region.
+`--steps K` is the number of timed steps; `ms_per_step` in the JSON line is the time of one of them. `--dump-outputs DIR`
+writes, after the timed window, the outputs of its last step (the (B, 8) poses a caller of the timed path receives) as
+DIR/y.npy (float32); inputs and weights are seeded, so the same arguments give the same inputs on every run.
 
 The plain single-GPU command (`python bench.py [--gpus 1 --steps K --warmup W]`, the driver's) measures the headline window first
 (a child process of its own) and then attaches a `secondary` block: steady state over 200 steps, --strict, ring scans, c4, c5 and
@@ -490,7 +493,10 @@ def parse_args(argv=None):
     ap.add_argument('--force-dist', action='store_true',
                     help='initialise the RCCL process group even for one rank (exercises the all-gather path on one GPU)')
     ap.add_argument('--ahead', default='knn', choices=['sample', 'features', 'knn'], help='stages run ahead')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed window, write the outputs of its last step as DIR/<name>.npy (float32)')
     args = ap.parse_args(argv)
+    group_given = args.group is not None
     wl = CONFIGS[args.config]
     if args.strict:
         if args.group not in (None, 1) or args.dense_group not in (None, 0):
@@ -513,13 +519,35 @@ def parse_args(argv=None):
         ap.error('--latency is a single-GPU, single-pair mode')
     if args.cpu_stub:
         args.no_overlap = True                      # the stand-in has no stages to overlap
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
     dense = bool(args.dense_group) and args.ahead == 'knn' and args.group > 1 and not args.no_overlap and not args.sequence
     if dense and not args.latency and not args.alone_only and args.steps % args.group != 0:
         # a dense (and a sampling) launch covers `group` batches and is enqueued at a group boundary only: a window that
         # is not a whole number of groups would credit work it did not do (or do work it does not credit)
-        ap.error('--steps {} is not a multiple of --group {}: with dense groups the timed window must hold whole '
-                 'groups (use --steps {})'.format(args.steps, args.group, -(-args.steps // args.group) * args.group))
+        if group_given:
+            ap.error('--steps {} is not a multiple of --group {}: with dense groups the timed window must hold whole '
+                     'groups (use --steps {})'.format(args.steps, args.group, -(-args.steps // args.group) * args.group))
+        # the configuration's group size: the largest that divides the window, so that --steps is the window it asks for
+        args.group = max(g for g in range(1, args.group + 1) if args.steps % g == 0)
     return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: each array as <directory>/<name>.npy, float32 (float64 stays float64), 64 MB at most in all."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        out[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('bench.py: --dump-outputs: {} bytes exceed the {} byte limit'.format(total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
 
 
 class OutputGather:
@@ -623,7 +651,7 @@ def run_latency(args, model, cfg, sd, kind, points, dev):
     from deepclr_amd.models import ModelInferenceHelper
     x = torch.from_numpy(synthetic.make_batch(kind, 1, points)).to(dev)
     out = {}
-    iters = max(args.steps, 20)
+    iters = args.steps
     for seq in (False, True):
         helper = ModelInferenceHelper(model, is_sequential=seq)
         if seq:
@@ -715,7 +743,7 @@ def run(args):
         med = lat['pairwise']['median_ms']
         result = {
             'metric': 'scan-pairs/sec (2x{} pts)'.format(points), 'value': 1e3 / med, 'unit': 'scan-pairs/s',
-            'n_gpus': 1, 'steps': max(args.steps, 20), 'warmup': args.warmup, 'ms_per_step': med,
+            'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': med,
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': 'f32 (matrix products: f16 hi/lo split operands, f32 accumulate)' if ops.PRECISION == 'f16x2' else 'f32',
             'data': 'synthetic',
@@ -730,6 +758,8 @@ def run(args):
             result['pose_delta_vs_oracle'] = pose_deltas(y.view(1, -1), x, cfg, sd, 1, False)[0]
             if not args.no_cpu_leg:
                 result['cpu_baseline'] = cpu_baseline(cfg, sd, cloud_kind, points)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {'y': y.detach().view(1, -1).cpu().numpy()})
         print(json.dumps(result), flush=True)
         return
 
@@ -964,6 +994,8 @@ def run(args):
             host_trace.append(time.perf_counter() - t0)
     fence()
     elapsed = time.perf_counter() - t0
+    # the last timed step's outputs, copied before the untimed passes below can rewrite the buffers they live in
+    last_outputs = y.detach().cpu().numpy() if args.dump_outputs else None
     if prof is not None:
         import pstats
         prof.disable()
@@ -1145,6 +1177,8 @@ def run(args):
                                        'batches': len(recent_kept) or 1, 'rank': 0}
             if world == 1 and not args.no_cpu_leg:
                 result['cpu_baseline'] = cpu_baseline(cfg, sd, cloud_kind, points, budget_s=6.0, pairs_cfg=pairs_cfg)
+        if last_outputs is not None:
+            dump_outputs(args.dump_outputs, {'y': last_outputs})
         print(json.dumps(result), flush=True)
     if use_dist:
         dist.barrier()
@@ -1177,7 +1211,7 @@ SECONDARY_TIMEOUT_S = 120            # per child; a child that fails or overruns
 HEADLINE_TIMEOUT_S = 600
 SECONDARY_DEADLINE_S = 420           # for ALL secondary passes together: past it the remaining ones are skipped (recorded as such),
                                      # so that headline + secondaries stay inside the driver's limit whatever hangs
-PLAIN_FLAGS = ('--gpus', '--steps', '--warmup', '--config', '--pose-budget')
+PLAIN_FLAGS = ('--gpus', '--steps', '--warmup', '--config', '--pose-budget', '--dump-outputs')
 
 
 def under_profiler() -> bool:

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -78,16 +79,24 @@ def test_peaks_and_workload_constants(bench):
 
 def test_measurement_modes_and_the_whole_groups_rule(bench, capsys):
     """--strict / --h2d / --clouds ring / --latency beside the headline; with dense groups a timed window that is not a
-    whole number of groups would credit work it did not do: rejected."""
+    whole number of groups would credit work it did not do: an explicit --group that does not divide
+    --steps is rejected, and the configuration's own group size shrinks to the largest one that divides the window, so
+    that --steps is always the number of timed steps."""
     args = bench.parse_args(['--strict', '--steps', '7'])
     assert (args.group, args.dense_group, args.depth, args.dense_streams, args.steps) == (1, 0, 6, 4, 7)
     assert bench.parse_args([]).dense_streams == 1 and bench.parse_args(['--strict', '--depth', '3']).depth == 3
     with pytest.raises(SystemExit):
         bench.parse_args(['--strict', '--group', '4'])
-    for bad in (['--steps', '25', '--warmup', '5'], ['--config', 'c5', '--steps', '30']):
+    for bad in (['--steps', '25', '--warmup', '5', '--group', '10'], ['--config', 'c5', '--steps', '30', '--group', '20']):
         with pytest.raises(SystemExit):
             bench.parse_args(bad)
         assert 'whole' in capsys.readouterr().err
+    for argv, group in ((['--steps', '25', '--warmup', '5'], 5), (['--config', 'c5', '--steps', '30'], 15),
+                        (['--steps', '7'], 7), (['--steps', '23'], 1), (['--steps', '20'], 10), (['--steps', '1'], 1)):
+        args = bench.parse_args(argv)
+        assert args.steps == int(argv[argv.index('--steps') + 1]) and args.group == group and args.steps % args.group == 0
+    with pytest.raises(SystemExit):
+        bench.parse_args(['--steps', '0'])
     assert bench.parse_args(['--steps', '30']).steps == 30                        # c2: groups of 10
     assert bench.parse_args(['--steps', '25', '--dense-group', '0']).steps == 25   # no dense groups: any window
     assert bench.parse_args(['--steps', '25', '--no-overlap']).steps == 25
@@ -414,3 +423,37 @@ def test_eight_rank_launch_with_the_stub_gathers_on_every_rank(bench):
     assert line['collectives']['all_gathers'] == 4 and line['config']['parallelism'] == 'dp8'     # 1 in the warm-up + 3
     if len(os.sched_getaffinity(0)) >= 8:
         assert line['host_cores_of_rank0'] is not None
+
+
+def test_dump_outputs_writes_the_last_timed_step(bench, tmp_path):
+    """--dump-outputs DIR: after the timed window, the outputs of its LAST step as DIR/y.npy (float32), the same on
+    every run with the same arguments; --steps is the number of timed steps. Run on the CPU stand-in, whose outputs
+    encode the step that produced them (warm-up steps count first)."""
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    got = []
+    for run in range(2):
+        out = tmp_path / ('dump%d' % run)
+        done = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--cpu-stub', '--steps', '7',
+                               '--warmup', '2', '--dump-outputs', str(out)], env=env, capture_output=True, text=True,
+                              timeout=300)
+        assert done.returncode == 0, done.stderr[-2000:]
+        lines = [l for l in done.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line['steps'] == 7 and line['ms_per_step'] > 0
+        assert sorted(os.listdir(str(out))) == ['y.npy']
+        y = np.load(str(out / 'y.npy'))
+        assert y.dtype == np.float32 and y.shape == (bench.PAIRS_PER_GPU, 8)
+        assert (y == 2 + 7 - 1).all()                                          # the 9th step: 2 warm-up + 7 timed
+        got.append(y)
+    assert np.array_equal(got[0], got[1])
+
+
+def test_dump_outputs_casts_to_float32_and_keeps_to_the_size_limit(bench, tmp_path):
+    bench.dump_outputs(str(tmp_path / 'a'), {'y': np.arange(6, dtype=np.float16).reshape(2, 3),
+                                             'z': np.ones(3, dtype=np.float64)})
+    assert np.load(str(tmp_path / 'a' / 'y.npy')).dtype == np.float32
+    assert np.load(str(tmp_path / 'a' / 'z.npy')).dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / 'b'), {'y': np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
+    assert not os.path.exists(str(tmp_path / 'b'))

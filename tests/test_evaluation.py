@@ -1,5 +1,8 @@
 """Result-file format and odometry metrics against fixtures written by the reference's evaluation code
-(tests/golden/make_eval_golden.py)."""
+(tests/golden/make_eval_golden.py) and by its evaluation scripts (tests/golden/make_eval_script_golden.py)."""
+import csv
+import io
+import json
 import os
 
 import numpy as np
@@ -217,28 +220,69 @@ def test_evaluation_flow_of_the_reference_script(tmp_path):
     assert counted == len(total) - (a['speed'] == a['speed'].min()).sum()
 
 
-REFERENCE_SCRIPT = '/root/reference/scripts/evaluation.py'
+def _script_record():
+    """What the reference's scripts/evaluation.py and scripts/paper/kitti_*_table.py left on the run directories of
+    `_write_run` (tests/golden/make_eval_script_golden.py): CSV texts, the other files by path, the tables' stdout."""
+    with open(os.path.join(GOLDEN, 'eval_script_outputs.json')) as f:
+        return json.load(f)
 
 
-@pytest.mark.skipif(not os.path.isfile(REFERENCE_SCRIPT), reason="the reference tree exists in the build container only")
+def _csv_rows(text):
+    return list(csv.DictReader(io.StringIO(text)))
+
+
+def _column_value(container, column):
+    """The figure a column of the script's tables holds, read off this package's container: `<t|r>_<metric>_<stat>
+    [unit]` is the `<stat>.<translation|rotation>.<metric>` attribute, `time_<stat> [ms]` is `<stat>.time`; angles are
+    tabulated in degrees and a `%` column is the (per-metre) translation x 100."""
+    name, unit = column[:-1].split(' [')
+    if name.startswith('time_'):
+        return getattr(container, name[len('time_'):]).time
+    part, metric, stat = name.split('_')
+    value = getattr(getattr(getattr(container, stat), {'t': 'translation', 'r': 'rotation'}[part]), metric)
+    if unit.startswith('deg'):
+        return np.rad2deg(value)
+    return value * 100 if unit == '%' else value
+
+
+def _check_rows(rows, containers):
+    """Every numeric column of every row equals the figure this package's container for that row gives."""
+    assert [r['name'] for r in rows] == list(containers)
+    for row in rows:
+        for column, text in row.items():
+            if column in ('name', 'method', 'params'):
+                continue
+            np.testing.assert_allclose(_column_value(containers[row['name']], column), float(text), rtol=1e-9,
+                                       atol=1e-15, err_msg='{} {}'.format(row['name'], column))
+
+
+def _evaluate_run(d):
+    from deepclr.evaluation import Evaluator, load_scenario
+    scenario = load_scenario(os.path.join(d, 'scenario.yaml'), with_method=True)
+    return scenario, Evaluator.read(d, ['{}.txt'.format(k) for k in scenario.data.keys()])
+
+
+FIGURES = {'segment_errors': 'plot_segment_error_bars', 'plot_eot': 'plot_error_over_time',
+           'plot_error': 'plot_kitti_errors', 'plot_path': 'plot_sequences', 'plot_path2d': 'plot_sequences_2d'}
+
+
 def test_reference_evaluation_script_runs_on_this_builds_output(tmp_path):
-    """f3 end to end: the reference's own scripts/evaluation.py, importing `deepclr` from this repository, evaluates
-    run directories written here (single and multi-run mode) and its CSV columns carry the golden statistics."""
-    import csv
-    import subprocess
-    import sys
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PYTHONPATH=repo, MPLBACKEND='Agg')
-    base = str(tmp_path)
-    _write_run(base, 'run0', 'DEEPCLR')
-    _write_run(base, 'run1', 'DEEPCLR', sequential=False)
-    for argv in ([os.path.join(base, 'run0')], [base, '--scenario', 'demo']):
-        done = subprocess.run([sys.executable, REFERENCE_SCRIPT] + argv, env=env, cwd=base, capture_output=True,
-                              text=True, timeout=600)
-        assert done.returncode == 0, done.stderr[-2000:]
+    """f3 end to end: the reference's own scripts/evaluation.py, importing `deepclr` from this repository, evaluated
+    run directories written here (single and multi-run mode; its outputs are stored in
+    tests/golden/eval_script_outputs.json). Every figure of its CSV tables is read again off this package's containers
+    through the attributes the script names in the column headers, the tables carry the golden statistics, and every
+    figure file it saved is drawn again here."""
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
     want = _expected()
-    out = os.path.join(base, 'run0', 'evaluation')
-    rows = {r['name']: r for r in csv.DictReader(open(os.path.join(out, 'step_errors.csv')))}
+    rec = _script_record()['evaluation']
+    base = str(tmp_path)
+    runs = {name: _evaluate_run(_write_run(base, name, 'DEEPCLR', sequential=name == 'run0')) for name in ('run0', 'run1')}
+    scenario, evaluator = runs['run0']
+    steps = dict(evaluator.get_step_errors(), TOTAL=evaluator.get_total_step_errors())
+    _check_rows(_csv_rows(rec['csv']['run0/evaluation/step_errors.csv']), steps)
+    rows = {r['name']: r for r in _csv_rows(rec['csv']['run0/evaluation/step_errors.csv'])}
     assert list(rows) == ['a', 'b', 'TOTAL']
     for name, key in (('a', 'step_a'), ('b', 'step_b'), ('TOTAL', 'step_total')):
         mean, std, mx = want[key + '_mean'], want[key + '_std'], want[key + '_max']
@@ -247,41 +291,83 @@ def test_reference_evaluation_script_runs_on_this_builds_output(tmp_path):
             [float(got['t_kitti_mean [m]']), float(got['t_rmse_std [m]']), float(got['r_kitti_max [deg]']),
              float(got['r_chordal_mean [deg]']), float(got['time_mean [ms]']), float(got['time_max [ms]'])],
             [mean[0], std[1], np.rad2deg(mx[2]), np.rad2deg(mean[3]), mean[4], mx[4]], rtol=2e-6)
-    rows = {r['name']: r for r in csv.DictReader(open(os.path.join(out, 'segment_errors.csv')))}
+    segments = dict(evaluator.get_segment_errors(), TOTAL=evaluator.get_total_segment_errors())
+    _check_rows(_csv_rows(rec['csv']['run0/evaluation/segment_errors.csv']), segments)
+    rows = {r['name']: r for r in _csv_rows(rec['csv']['run0/evaluation/segment_errors.csv'])}
     mean, std = want['seg_total_mean'], want['seg_total_std']
     np.testing.assert_allclose(
         [float(rows['TOTAL']['t_kitti_mean [%]']), float(rows['TOTAL']['r_kitti_std [deg/m]']),
          float(rows['TOTAL']['r_rmse_mean [deg/m]'])],
         [mean[0] * 100, np.rad2deg(std[2]), np.rad2deg(mean[4])], rtol=2e-6)
+    # every file the script saved (run0 only: run1 is not sequential and has no figures) is drawn again from this package
+    assert not any(path.startswith('run1/') for path in rec['other_files'])
     for sub in ('segment_errors.png', 'plot_eot/a.pdf', 'plot_error/b.png', 'plot_path/a.png', 'plot_path2d/b.pdf'):
-        assert os.path.getsize(os.path.join(out, sub)) > 1000
-    multi = os.path.join(base, 'evaluation', 'demo')
-    rows = list(csv.DictReader(open(os.path.join(multi, 'demo_step_errors.csv'))))
+        assert rec['other_files']['run0/evaluation/' + sub] > 1000
+    saved = {}                                                         # figure source -> {sequence or None: [paths]}
+    for path in rec['other_files']:
+        parts = path.split('/')
+        assert parts[:2] == ['run0', 'evaluation'] and len(parts) in (3, 4), path
+        source = os.path.splitext(parts[2])[0] if len(parts) == 3 else parts[2]
+        key = None if len(parts) == 3 else os.path.splitext(parts[3])[0]
+        saved.setdefault(source, {}).setdefault(key, []).append(path)
+    for source, by_key in sorted(saved.items()):
+        figs = getattr(evaluator, FIGURES[source])()
+        if None not in by_key:
+            assert list(figs) == ['a', 'b'] == sorted(by_key)
+        for key, paths in by_key.items():
+            fig = figs if key is None else figs[key]
+            for path in paths:
+                out = tmp_path / ('drawn_' + path.replace('/', '_'))
+                fig.savefig(str(out), dpi=40)
+                assert out.stat().st_size > 1000, path
+        plt.close('all')
+    # multi-run mode: one row per run directory of the scenario, method and parameters from its scenario.yaml
+    rows = _csv_rows(rec['csv']['evaluation/demo/demo_step_errors.csv'])
     assert [r['name'] for r in rows] == ['run0', 'run1'] and rows[0]['method'] == 'DEEPCLR'
     assert 'model_name=run1' in rows[1]['params']
-    assert len(list(csv.DictReader(open(os.path.join(multi, 'demo_segment_errors.csv'))))) == 1   # run1: not sequential
-    assert not os.path.isdir(os.path.join(base, 'run1', 'evaluation', 'plot_path'))
+    for row in rows:
+        scen = runs[row['name']][0]
+        assert scen.name == 'demo' and row['method'] == scen.method.name
+        assert all('{}={}'.format(k, v) in row['params'] for k, v in scen.method.params.items())
+    _check_rows(rows, {name: ev_.get_total_step_errors() for name, (_, ev_) in runs.items()})
+    rows = _csv_rows(rec['csv']['evaluation/demo/demo_segment_errors.csv'])
+    assert len(rows) == 1 and scenario.sequential and not runs['run1'][0].sequential     # run1: not sequential
+    _check_rows(rows, {'run0': evaluator.get_total_segment_errors()})
+    _check_rows(_csv_rows(rec['csv']['run1/evaluation/step_errors.csv']),
+                dict(runs['run1'][1].get_step_errors(), TOTAL=runs['run1'][1].get_total_step_errors()))
 
 
-@pytest.mark.skipif(not os.path.isfile(REFERENCE_SCRIPT), reason="the reference tree exists in the build container only")
+def _printed(texts, values):
+    """Figures a pandas table printed (6 decimals at most) against the values they were printed from."""
+    assert len(texts) == len(values)
+    for text, value in zip(texts, values):
+        assert abs(float(text) - value) <= 5e-7 * (1 + 1e-9), (text, value)
+
+
 @pytest.mark.parametrize('script,scenario,expect', [
     ('kitti_odometry_table.py', 'kitti_04_10', ('t_rmse [m]', 'r_rmse [deg]', 'Average Inference Time')),
     ('kitti_artificial_table.py', 'kitti_pairs', ('Rot. Error Mean [deg]', 'Time [ms]')),
 ])
 def test_reference_paper_tables_read_this_builds_output(tmp_path, script, scenario, expect):
-    """scripts/paper/*_table.py (the tables of the publication) on a run directory written here: they read
-    `metrics.<stat>.<part>.<metric>` and `.time` off the containers."""
-    import subprocess
-    import sys
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = str(tmp_path)
-    _write_run(base, 'run0', 'DEEPCLR', scenario=scenario)
-    done = subprocess.run([sys.executable, os.path.join(os.path.dirname(REFERENCE_SCRIPT), 'paper', script), base],
-                          env=dict(os.environ, PYTHONPATH=repo, MPLBACKEND='Agg'), cwd=base, capture_output=True,
-                          text=True, timeout=300)
-    assert done.returncode == 0, done.stderr[-2000:]
+    """scripts/paper/*_table.py (the tables of the publication) on a run directory written here (their stdout is
+    stored in tests/golden/eval_script_outputs.json): they read `metrics.<stat>.<part>.<metric>` and `.time` off the
+    containers, and the figures they printed are the ones this package's containers give."""
+    stdout = _script_record()['paper'][script]
     for word in expect:
-        assert word in done.stdout, done.stdout[-1500:]
+        assert word in stdout, stdout[-1500:]
+    found, evaluator = _evaluate_run(_write_run(str(tmp_path), 'run0', 'DEEPCLR', scenario=scenario))
+    assert found.name == scenario and found.method.name == 'DEEPCLR'
+    total = evaluator.get_total_step_errors()
     want = _expected()
+    if script == 'kitti_odometry_table.py':
+        lines = stdout.splitlines()
+        for seq, metrics in evaluator.get_step_errors().items():
+            row = [l for l in lines if l.split()[:1] == [seq]]
+            assert len(row) == 1, stdout
+            _printed(row[0].split()[1:], [metrics.mean.translation.rmse, np.rad2deg(metrics.mean.rotation.rmse)])
+        assert 'Average Inference Time: {:.2f} ms'.format(total.mean.time) in stdout
     if script == 'kitti_artificial_table.py':                 # one row of totals (pandas elides the middle columns at 80 characters)
-        assert '{:.6f}'.format(np.rad2deg(want['step_total_mean'][3])) in done.stdout
+        assert '{:.6f}'.format(np.rad2deg(want['step_total_mean'][3])) in stdout
+        row = [l for l in stdout.splitlines() if l.startswith('DEEPCLR')]
+        assert len(row) == 1 and row[0].split()[2] == '...'
+        _printed(row[0].split()[1::2], [np.rad2deg(total.mean.rotation.chordal), total.mean.time])

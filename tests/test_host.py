@@ -294,11 +294,10 @@ def test_load_config_and_tensor_backed_loader_for_timing_script(tmp_path):
     nomodel.write_text("device: cuda\n")
     with pytest.raises(RuntimeError, match='missing required parameters'):
         load_config(str(nomodel), Mode.TEST)
-    ref = '/root/reference/configs/training/kitti_00-06.yaml'              # the reference's own files, where present
-    if os.path.exists(ref):
-        cfg3 = load_config(ref, Mode.TEST)
-        assert cfg3.identifier == 'kitti_00-06' and cfg3.model.input_dim == 4 and cfg3.data_loader.batch_size == 5
-        assert cfg3.model.params.output.params.mlp == [256, 256, 512, 512, 1024]
+    # the reference's own training configuration (a child of its kitti_base.yaml), stored as fixtures
+    cfg3 = load_config(os.path.join(root, 'tests', 'golden', 'configs', 'kitti_00-06.yaml'), Mode.TEST)
+    assert cfg3.identifier == 'kitti_00-06' and cfg3.model.input_dim == 4 and cfg3.data_loader.batch_size == 5
+    assert cfg3.model.params.output.params.mlp == [256, 256, 512, 512, 1024]
 
 
 def test_entry_points_reject_bad_arguments_before_touching_the_gpu():
