@@ -8,9 +8,6 @@
 //           split and stored in place as half-octets of layer 3's input;
 //   layer 3 computes H2 * W3^T -- lane = channel, lane-quarter = template point, registers = its 4
 //           neighbours of the tile, so mask + max over the k neighbours stays in registers.
-#ifdef DCLR_ABLATION
-#include <stdlib.h>
-#endif
 
 #include "mma16f.h"
 
@@ -30,22 +27,14 @@ constexpr int F16_KG = F16_C / 32;              // 4 k-steps of 32
 __host__ __device__ constexpr int f16_octet_offset(int o) { return 256 * (o & 1) + 128 * ((o >> 1) & 1) + 32 * (o >> 2); }
 
 // One pass over K for T row tiles x 2 channel tiles. TRANSPOSED: weights are the A operand.
-// ABL (timing-only ablations, results wrong): bit 0 = no gather round trips in phase A (rows built from constants),
-// bit 1 = weight fragments always from k-step 0 of tile 0 (no weight streaming), bit 2 = no phase A at all, bit 3 = no weight
-// loads at all (80 pairs: 497 us; ABL 1 / 2 / 8 / 9 / 4 / 12: 465 / 457 / 414 / 385 / 366 / 298)
-template <int T, bool TRANSPOSED, int ABL = 0>
+template <int T, bool TRANSPOSED>
 __device__ __forceinline__ void flow16_panel(dclr_f32x4 (&acc)[T][2], dclr_f32x4 (&acc2)[T][2], const char *a_lane,
                                              const float4 *wh_lane, const float4 *wl_lane, int tile_stride) {
     dclr_h8 h0[2], l0[2], h1[2], l1[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        if constexpr (ABL & 8) {                                  // timing probe: no weight loads at all
-            h0[u] = __builtin_bit_cast(dclr_h8, make_float4(1.f, 2.f, (float)u, 3.f));
-            l0[u] = h0[u];
-        } else {
-            h0[u] = dclr_frag_h8(wh_lane + (size_t)u * tile_stride);
-            l0[u] = dclr_frag_h8(wl_lane + (size_t)u * tile_stride);
-        }
+        h0[u] = dclr_frag_h8(wh_lane + (size_t)u * tile_stride);
+        l0[u] = dclr_frag_h8(wl_lane + (size_t)u * tile_stride);
     }
     auto step = [&](int g, const dclr_h8 (&wh)[2], const dclr_h8 (&wl)[2]) {
 #pragma unroll
@@ -67,22 +56,16 @@ __device__ __forceinline__ void flow16_panel(dclr_f32x4 (&acc)[T][2], dclr_f32x4
     for (int g = 0; g < F16_KG; g += 2) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            if constexpr (ABL & 10) { h1[u] = l0[u]; l1[u] = h0[u]; }
-            else {
             h1[u] = dclr_frag_h8(wh_lane + (size_t)u * tile_stride + (size_t)(g + 1) * 64);
             l1[u] = dclr_frag_h8(wl_lane + (size_t)u * tile_stride + (size_t)(g + 1) * 64);
-            }
         }
         __builtin_amdgcn_sched_barrier(0);
         step(g, h0, l0);
         if (g + 2 < F16_KG) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                if constexpr (ABL & 10) { h0[u] = l1[u]; l0[u] = h1[u]; }
-                else {
                 h0[u] = dclr_frag_h8(wh_lane + (size_t)u * tile_stride + (size_t)(g + 2) * 64);
                 l0[u] = dclr_frag_h8(wl_lane + (size_t)u * tile_stride + (size_t)(g + 2) * 64);
-                }
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -90,7 +73,7 @@ __device__ __forceinline__ void flow16_panel(dclr_f32x4 (&acc)[T][2], dclr_f32x4
     }
 }
 
-template <int T, int ABL = 0>
+template <int T>
 __global__ __launch_bounds__(256, T <= 5 ? 3 : 2) void flow16_kernel(int pairs, int npoint, int k, float radius,
                                                      const float *__restrict__ f_rows,
                                                      const int32_t *__restrict__ knn_idx,
@@ -125,7 +108,7 @@ __global__ __launch_bounds__(256, T <= 5 ? 3 : 2) void flow16_kernel(int pairs, 
     {
         const int p = wave;
         const size_t gp = g0 + p;
-        const bool live = gp < total && !(ABL & 4);                     // wave-uniform
+        const bool live = gp < total;                                   // wave-uniform
         uint32_t bits = 0;
         int s_done = 0;
         float peak = 0.f;
@@ -144,10 +127,9 @@ __global__ __launch_bounds__(256, T <= 5 ? 3 : 2) void flow16_kernel(int pairs, 
             // a slot the search left unfilled (-1: fewer than k candidates within the 1e10 start distance of the slots, or
             // NaN coordinates; upstream fails at its .view(2, G, k) there) reads row 0 and is masked like a neighbour
             // beyond the radius: no address ever leaves the source cloud
-            const int raw_nb = (ABL & 1) ? (lane & 15) : (lane < k ? knn_idx[gp * k + lane] : 0);
+            const int raw_nb = lane < k ? knn_idx[gp * k + lane] : 0;
             const int my_nb = raw_nb < 0 ? 0 : raw_nb;
-            const float4 nbp = (ABL & 1) ? make_float4(tx + lane, ty, tz, 0.f)
-                                         : *reinterpret_cast<const float4 *>(f_rows + (src0 + my_nb) * DCLR_F_STRIDE + 64);
+            const float4 nbp = *reinterpret_cast<const float4 *>(f_rows + (src0 + my_nb) * DCLR_F_STRIDE + 64);
             const float my_dx = nbp.x - tx, my_dy = nbp.y - ty, my_dz = nbp.z - tz;
             const float norm = sqrtf(my_dx * my_dx + my_dy * my_dy + my_dz * my_dz);
             bits = (uint32_t)__ballot(lane < k && raw_nb >= 0 && (!(radius > 0.f) || norm < radius));
@@ -157,7 +139,7 @@ __global__ __launch_bounds__(256, T <= 5 ? 3 : 2) void flow16_kernel(int pairs, 
 #pragma unroll
             for (int s = 0; s < KMAX; ++s) {
                 const int nb = __builtin_amdgcn_readlane(my_nb, s < k ? s : 0);     // s >= k: a harmless repeat
-                psv[s] = (ABL & 1) ? make_float2(0.01f * nb, 0.02f * lane) : *reinterpret_cast<const float2 *>(psrow + (size_t)nb * F16_C);
+                psv[s] = *reinterpret_cast<const float2 *>(psrow + (size_t)nb * F16_C);
             }
             const float2 ptv = *reinterpret_cast<const float2 *>(pt + gp * F16_C + 2 * lane);
             const float2 bv = *reinterpret_cast<const float2 *>(b1 + 2 * lane);
@@ -209,7 +191,7 @@ __global__ __launch_bounds__(256, T <= 5 ? 3 : 2) void flow16_kernel(int pairs, 
             }
         }
         const float4 *wh = w2p + (size_t)(2 * wave) * F16_KG * 64 + lane;
-        flow16_panel<T, true, ABL>(acc, acc2, a_lane, wh, wh + (size_t)(F16_C / 16) * F16_KG * 64, F16_KG * 64);
+        flow16_panel<T, true>(acc, acc2, a_lane, wh, wh + (size_t)(F16_C / 16) * F16_KG * 64, F16_KG * 64);
         __syncthreads();                                   // every wave has consumed the layer-1 rows
         float peak = 0.f;
 #pragma unroll
@@ -262,7 +244,7 @@ __global__ __launch_bounds__(256, T <= 5 ? 3 : 2) void flow16_kernel(int pairs, 
                 }
             }
             const float4 *wh = w3p + (size_t)tile0 * F16_KG * 64 + lane;
-            flow16_panel<T, false, ABL>(acc, acc2, a_lane, wh, wh + (size_t)(F16_OUT / 16) * F16_KG * 64, F16_KG * 64);
+            flow16_panel<T, false>(acc, acc2, a_lane, wh, wh + (size_t)(F16_OUT / 16) * F16_KG * 64, F16_KG * 64);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 float mx = 0.f;                            // ReLU output floor
@@ -282,13 +264,13 @@ __global__ __launch_bounds__(256, T <= 5 ? 3 : 2) void flow16_kernel(int pairs, 
     }
 }
 
-template <int T, int ABL = 0>
+template <int T>
 void flow16_launch(int pairs, int npoint, int k, float radius, const float *f_rows, const int32_t *knn_idx,
                    const float *pt, const float *ps, const float *w1a, const float *b1, const void *w2p,
                    const float *b2, const void *w3p, const float *b3, float *e_rows, hipStream_t stream,
                    float *zero = nullptr, long long zero_count = 0, uint32_t *overflow = nullptr) {
     const size_t total = (size_t)pairs * npoint;
-    hipLaunchKernelGGL((flow16_kernel<T, ABL>), dim3((unsigned)((total + F16_G - 1) / F16_G)), dim3(256), 0, stream, pairs,
+    hipLaunchKernelGGL((flow16_kernel<T>), dim3((unsigned)((total + F16_G - 1) / F16_G)), dim3(256), 0, stream, pairs,
                        npoint, k, radius, f_rows, knn_idx, pt, ps, w1a, b1, reinterpret_cast<const float4 *>(w2p), b2,
                        reinterpret_cast<const float4 *>(w3p), b3, e_rows, zero, zero_count, overflow);
 }
@@ -308,9 +290,6 @@ void flow16_launch(int pairs, int npoint, int k, float radius, const float *f_ro
 //   layer 3: H2 * W3^T  -- wave w owns channel tiles 2 w, 2 w + 1, one at a time; lane = channel, registers = rows
 //            8 g4 + 4 h + i of each tile: four consecutive rows of ONE point (4 T is a multiple of 4).
 constexpr int F32_KG = F16_C / 16;               // 8 k-steps of 16
-#ifndef DCLR_FLOW32_ABL
-#define DCLR_FLOW32_ABL 0        // timing builds only (results wrong): bit 0 = no phase A (zero rows), bit 1 = no weight loads
-#endif
 
 #ifdef DCLR_FLOW_STAMPS          // measurement builds only: cycle stamps of every 64th workgroup (scratch/flow_stamps.py)
 constexpr int F32_NSTAMP = 10, F32_STAMP_BLOCKS = 1024;
@@ -333,15 +312,10 @@ __device__ __forceinline__ void flow32_panel(dclr_f32x16 (&acc)[RT], dclr_f32x16
             l[t] = dclr_lds_h8(a_lane + t * 32 * F16_STRIDE + 64 * g + 16);
         }
     };
-#if DCLR_FLOW32_ABL & 2
-#define F32_FRAG(p) __builtin_bit_cast(dclr_h8, make_float4(1.f, 2.f, 3.f, (float)((size_t)(p) & 255)))
-#else
-#define F32_FRAG(p) dclr_frag_h8(p)
-#endif
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
-        wh[g] = F32_FRAG(wh_lane + (size_t)g * 64);
-        wl[g] = F32_FRAG(wl_lane + (size_t)g * 64);
+        wh[g] = dclr_frag_h8(wh_lane + (size_t)g * 64);
+        wl[g] = dclr_frag_h8(wl_lane + (size_t)g * 64);
     }
     // AHEAD costs 8 RT registers: with three workgroups per CU (RT <= 3, 168 registers) it spills, and three waves per SIMD
     // cover an LDS round trip anyway
@@ -351,8 +325,8 @@ __device__ __forceinline__ void flow32_panel(dclr_f32x16 (&acc)[RT], dclr_f32x16
     for (int g = 0; g < F32_KG; ++g) {
         __builtin_amdgcn_sched_barrier(0);
         if (g + 3 < F32_KG) {
-            wh[(g + 3) & 3] = F32_FRAG(wh_lane + (size_t)(g + 3) * 64);
-            wl[(g + 3) & 3] = F32_FRAG(wl_lane + (size_t)(g + 3) * 64);
+            wh[(g + 3) & 3] = dclr_frag_h8(wh_lane + (size_t)(g + 3) * 64);
+            wl[(g + 3) & 3] = dclr_frag_h8(wl_lane + (size_t)(g + 3) * 64);
         }
         if constexpr (AHEAD) {
             if (g + 1 < F32_KG) read_act(g + 1, ah[(g + 1) & 1], al[(g + 1) & 1]);
@@ -420,7 +394,7 @@ __global__ __launch_bounds__(256, T <= 6 ? 3 : 2) void flow32_kernel(int pairs, 
         uint32_t bits = 0;
         float peak = 0.f;
         char *const slot = tile + p * KP * F16_STRIDE + 32 * (lane >> 2) + 4 * (lane & 3);
-        if (gp < total && !(DCLR_FLOW32_ABL & 1)) {                       // wave-uniform
+        if (gp < total) {                                                 // wave-uniform
             // Two dependent L2 round trips behind the neighbour list (one index per lane): lane s fetches neighbour s's
             // position (offsets, norms and the radius mask for all neighbours at once) while the source halves of layer 1
             // (float2 per lane and row) are already on their way -- they depend on the list only.
@@ -628,16 +602,7 @@ extern "C" int dclr_debug_flow_stamps(unsigned long long *host_out, int blocks) 
 // (v_mfma_f32_16x16x32_f16, flow16_kernel) below, where the rows pad: k = 25..28 (112 rows in 128) 1154-1178 against
 // 1120-1135, k = 21..24 (96 in 96, but three tiles of 32 against six of 16 per wave) 932-940 against 896-930, k = 20 (80 rows
 // in 96) 632-658 against 517-541 per 80 x 1024 points (profiles/NOTES.md, round 6).
-// -DDCLR_FLOW_TILE16 / -DDCLR_FLOW_TILE32 (A/B builds) force one form for every k.
-static bool flow_uses_tile32(int k) {
-#if defined(DCLR_FLOW_TILE16)
-    return false;
-#elif defined(DCLR_FLOW_TILE32)
-    return true;
-#else
-    return (k + 3) / 4 >= 8;
-#endif
-}
+static bool flow_uses_tile32(int k) { return (k + 3) / 4 >= 8; }
 extern "C" int dclr_flow_f16_tile(int k) { return flow_uses_tile32(k) ? 32 : 16; }
 
 extern "C" int dclr_flow_embedding_fused_f16(int pairs, int npoint, int k, float radius, const float *f_rows,
@@ -659,33 +624,17 @@ int dclr_x_flow_embedding_fused_f16(int pairs, int npoint, int k, float radius, 
     DCLR_REQUIRE(((uintptr_t)w2p & 15) == 0 && ((uintptr_t)w3p & 15) == 0 && ((uintptr_t)pt & 7) == 0 &&
                  ((uintptr_t)ps & 7) == 0 && ((uintptr_t)b2 & 15) == 0);
     hipStream_t st = (hipStream_t)stream;
-#ifdef DCLR_ABLATION
-    // Measurement builds only (-DDCLR_ABLATION, a separate .so selected with DCLR_LIB; scratch/flow_probe.py): the
-    // timing-only variants return WRONG rows. The product library is compiled without them and reads no environment.
-    static const int abl = getenv("DCLR_FLOW_ABL") ? atoi(getenv("DCLR_FLOW_ABL")) : 0;      // k = 20 only
-    if (abl != 0 && (k + 3) / 4 == 5) {
-#define DCLR_FLOW16_ABL(A) case A: flow16_launch<5, A>(pairs, npoint, k, radius, f_rows, knn_idx, pt, ps, w1a, b1, w2p, b2, w3p, b3, e_rows, st); break
-        switch (abl) { DCLR_FLOW16_ABL(1); DCLR_FLOW16_ABL(2); DCLR_FLOW16_ABL(3); DCLR_FLOW16_ABL(4); DCLR_FLOW16_ABL(6); DCLR_FLOW16_ABL(8); DCLR_FLOW16_ABL(9); DCLR_FLOW16_ABL(12); default: break; }
-#undef DCLR_FLOW16_ABL
-        return dclr_launch_status();
-    }
-#endif
 #define DCLR_FLOW16_CASE(T) case T: flow16_launch<T>(pairs, npoint, k, radius, f_rows, knn_idx, pt, ps, w1a, b1, w2p, b2, w3p, b3, e_rows, st, zero, zero_count, overflow); break
-#define DCLR_FLOW32_CASE(T) case T: flow32_launch<T>(pairs, npoint, k, radius, f_rows, knn_idx, pt, ps, w1a, b1, w2p, b2, w3p, b3, e_rows, st, zero, zero_count, overflow); break
     if (flow_uses_tile32(k)) {
-        switch ((k + 3) / 4) {
-            DCLR_FLOW32_CASE(1); DCLR_FLOW32_CASE(2); DCLR_FLOW32_CASE(3); DCLR_FLOW32_CASE(4);
-            DCLR_FLOW32_CASE(5); DCLR_FLOW32_CASE(6); DCLR_FLOW32_CASE(7); DCLR_FLOW32_CASE(8);
-            default: return DCLR_E_UNSUPPORTED;
-        }
+        flow32_launch<8>(pairs, npoint, k, radius, f_rows, knn_idx, pt, ps, w1a, b1, w2p, b2, w3p, b3, e_rows, st, zero,
+                         zero_count, overflow);
     } else {
         switch ((k + 3) / 4) {
             DCLR_FLOW16_CASE(1); DCLR_FLOW16_CASE(2); DCLR_FLOW16_CASE(3); DCLR_FLOW16_CASE(4);
-            DCLR_FLOW16_CASE(5); DCLR_FLOW16_CASE(6); DCLR_FLOW16_CASE(7); DCLR_FLOW16_CASE(8);
+            DCLR_FLOW16_CASE(5); DCLR_FLOW16_CASE(6); DCLR_FLOW16_CASE(7);
             default: return DCLR_E_UNSUPPORTED;
         }
     }
 #undef DCLR_FLOW16_CASE
-#undef DCLR_FLOW32_CASE
     return dclr_launch_status();
 }

@@ -6,15 +6,6 @@
 // every operand split into f16 hi/lo halves, three instructions per product, f32 accumulation.
 #include "mma16f.h"
 
-#ifndef H16_PIPE
-#define H16_PIPE 3               // 3 (default since round 4): the activation fragments of step g + 1 are read while the MFMAs of
-                                 // step g run, and a step's loads / reads are dealt between its MFMAs (518 -> 496 us per 80 pairs);
-                                 // 1 = the read-ahead alone (515); 0 = round 3's loop (loads and reads in front of the MFMAs)
-#endif
-#ifndef H16_ABL
-#define H16_ABL 0                // timing probes of scratch/head_abl.sh only; the product library is built with 0
-#endif
-
 namespace {
 
 // ---- weight packing ------------------------------------------------------------------------------
@@ -78,23 +69,15 @@ __device__ __forceinline__ void head16_panel(dclr_f32x16 (&acc)[2][MT], dclr_f32
     // prefetch back into load-wait-use, see mma.h.)
     dclr_h8 wh[4][NT], wl[4][NT];
     auto fetch = [&](int g, dclr_h8 (&h)[NT], dclr_h8 (&l)[NT]) {
-#if H16_ABL & 1                  // timing probe: every step re-reads the first fragment (no stream from L2)
-        g = 0;
-#endif
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
-#if H16_ABL & 2                  // timing probe: no weight loads at all
-            h[u] = __builtin_bit_cast(dclr_h8, make_float4((float)g, 1.f, 2.f, (float)u));
-            l[u] = h[u];
-#else
             h[u] = dclr_frag_h8(wh_lane + (size_t)u * tile_stride + (size_t)g * 64);
             l[u] = dclr_frag_h8(wl_lane + (size_t)u * tile_stride + (size_t)g * 64);
-#endif
         }
     };
-#if H16_PIPE
-    // (H16_PIPE) the activation fragments of step g + 1 are read from LDS while the MFMAs of step g run (two register sets),
-    // and the step's loads and reads are dealt between its MFMAs instead of standing in front of them
+    // The activation fragments of step g + 1 are read from LDS while the MFMAs of step g run (two register sets), and the
+    // step's loads and reads are dealt between its MFMAs instead of standing in front of them (518 -> 496 us per 80 pairs;
+    // the read-ahead alone: 515)
     dclr_h8 ah2[2][MT], al2[2][MT];
     auto read_act = [&](int g, dclr_h8 (&h)[MT], dclr_h8 (&l)[MT]) {
 #pragma unroll
@@ -134,7 +117,6 @@ __device__ __forceinline__ void head16_panel(dclr_f32x16 (&acc)[2][MT], dclr_f32
                 fetch(ahead, wh[(i + 3) & 3], wl[(i + 3) & 3]);
                 read_act(nxt, ah2[(i + 1) & 1], al2[(i + 1) & 1]);
                 mfmas(wh[i], wl[i], ah2[i & 1], al2[i & 1]);
-#if H16_PIPE & 2
                 // deal the 2 NT loads and 2 MT reads between the 3 NT MT MFMAs
 #pragma unroll
                 for (int q = 0; q < 2 * NT; ++q) {
@@ -143,56 +125,10 @@ __device__ __forceinline__ void head16_panel(dclr_f32x16 (&acc)[2][MT], dclr_f32
                     __builtin_amdgcn_sched_group_barrier(0x100, (2 * MT + 2 * NT - 1) / (2 * NT), 0);
                 }
                 __builtin_amdgcn_sched_group_barrier(0x008, 3 * NT * MT, 0);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
     }
-#else
-    auto step = [&](int g, const dclr_h8 (&h)[NT], const dclr_h8 (&l)[NT]) {
-        dclr_h8 ah[MT], al[MT];
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-#if H16_ABL & 4                  // timing probe: no activation reads from LDS
-            ah[t] = __builtin_bit_cast(dclr_h8, make_float4((float)g, 1.f, 2.f, (float)t));
-            al[t] = ah[t];
-#else
-            ah[t] = dclr_lds_h8(a_lane + t * tile_bytes + 64 * g);
-            al[t] = dclr_lds_h8(a_lane + t * tile_bytes + 64 * g + 16);
-#endif
-        }
-#pragma unroll
-        for (int u = 0; u < NT; ++u)
-#pragma unroll
-            for (int t = 0; t < MT; ++t)
-                acc[u][t] = LAST ? dclr_mfma32(ah[t], h[u], acc[u][t]) : dclr_mfma32(h[u], ah[t], acc[u][t]);
-#pragma unroll
-        for (int u = 0; u < NT; ++u)
-#pragma unroll
-            for (int t = 0; t < MT; ++t)
-                acc2[u][t] = LAST ? dclr_mfma32(ah[t], l[u], acc2[u][t]) : dclr_mfma32(l[u], ah[t], acc2[u][t]);
-#pragma unroll
-        for (int u = 0; u < NT; ++u)
-#pragma unroll
-            for (int t = 0; t < MT; ++t)
-                acc2[u][t] = LAST ? dclr_mfma32(al[t], h[u], acc2[u][t]) : dclr_mfma32(h[u], al[t], acc2[u][t]);
-    };
-    fetch(0, wh[0], wl[0]);
-    fetch(kg > 1 ? 1 : 0, wh[1], wl[1]);
-    fetch(kg > 2 ? 2 : 0, wh[2], wl[2]);
-    for (int g = 0; g < kg; g += 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (g + i < kg) {                                          // wave-uniform
-                const int ahead = g + i + 3 < kg ? g + i + 3 : kg - 1;  // clamped: the load stays unconditional
-                fetch(ahead, wh[(i + 3) & 3], wl[(i + 3) & 3]);
-                __builtin_amdgcn_sched_barrier(0);
-                step(g + i, wh[i], wl[i]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-#endif
 }
 
 template <int MT>

@@ -28,7 +28,6 @@
 // Slots that would only repeat the first hit are skipped: max() over a multiset equals max() over
 // its support, so the result is identical. A centroid with no hit reproduces the published
 // behaviour (zero-filled index row => every slot is point 0).
-#include <stdlib.h>
 #include "mma16f.h"
 
 namespace {
@@ -93,7 +92,7 @@ __shared__ __attribute__((aligned(16))) float sa_w[SA_MAX_SCALES][SA_MLP_FLOATS]
 __device__ unsigned long long sa_dbg_w[16384][8];   // per wave, cycles: [0] total, [1] fast path incl. drains, [2] drains,
                                                    // [3] #drains, [4] sweep, [5] 1, [6] drain: point load, [7] drain: MLP + fold
 __shared__ unsigned long long sa_dbg_l[4][2];
-__device__ int getenv_dbg2 = 0;                    // harness switch: 1 = slice-path stamps in slots 4, 6, 7
+__device__ int sa_dbg_slice = 0;                    // harness switch: 1 = slice-path stamps in slots 4, 6, 7
 #define SA_STAMP(v) do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); } while (0)
 #endif
 
@@ -938,7 +937,7 @@ __global__ __launch_bounds__(SA_WAVES * 64, 4) void sa_msg_kernel(SaParams prm,
         unsigned long long *o = sa_dbg_w[(blockIdx.y * gridDim.x + blockIdx.x) * SA_WAVES + wave];
         o[0] = t_end - t_begin; o[1] = t_fast; o[2] = t_drain; o[3] = n_drain; o[4] = t_sweep; o[5] = 1ull;
         o[6] = sa_dbg_l[wave][0]; o[7] = sa_dbg_l[wave][1];
-        if (t_pre != 0 && getenv_dbg2) { o[4] = t_rows; o[6] = t_pre; o[7] = t_scan; }  // slice path: reported in place of sweep / drain detail
+        if (t_pre != 0 && sa_dbg_slice) { o[4] = t_rows; o[6] = t_pre; o[7] = t_scan; }  // slice path: reported in place of sweep / drain detail
     }
 #endif
 }
@@ -1006,9 +1005,8 @@ static int sa_launch(bool f16, int b, int n, int c, int npoint, const float *clo
     constexpr int per_wg = SA_WAVES * SA_CPW;
     dim3 grid((npoint + per_wg - 1) / per_wg, b);
     const int nch = prm.n_groups <= 64 ? 1 : 4;      // chunks of 64 group boxes per lane (128 groups: two of the four stay empty)
-    // slice-granular fetches: with slice boxes, or where a group IS one slice (A/B: DCLR_SA_PAIRS=1 keeps two groups per step)
-    static const bool pairs_only = getenv("DCLR_SA_PAIRS") != nullptr;
-    const bool slice_path = prm.slice_box != nullptr || (prm.group_pts && nch == 1 && prm.group_size == 64 && !pairs_only);
+    // slice-granular fetches: with slice boxes, or where a group IS one slice
+    const bool slice_path = prm.slice_box != nullptr || (prm.group_pts && nch == 1 && prm.group_size == 64);
 #define SA_LAUNCH(C_, NCH_, F_, SL_)                                                                                     \
     hipLaunchKernelGGL((sa_msg_kernel<C_, NCH_, F_, SL_>), grid, dim3(SA_WAVES * 64), 0, (hipStream_t)stream, prm, clouds, \
                        fps_idx, out_rows, counts)

@@ -12,7 +12,6 @@ Out of scope here: losses (a ground truth ``y`` raises), b
 """
 import abc
 import ctypes
-import os
 import time
 from typing import Any, Dict, List, Optional, Tuple
 
@@ -454,7 +453,7 @@ class OutputSimple(DeepCLRModule):
     def forward_rows(self, e_rows: torch.Tensor, pairs: int, precision: Optional[str] = None) -> torch.Tensor:
         precision = precision or ops.PRECISION
         layers = self._packed()
-        if self._fusable(layers, e_rows.shape[0], pairs, precision) and os.environ.get('DCLR_HEAD_FUSED', '1') != '0':
+        if self._fusable(layers, e_rows.shape[0], pairs, precision):
             if precision == 'f16x2':
                 g = ops.head_conv_fused_f16(e_rows, ops.E_STRIDE, self._packed_f16(), pairs)
             else:
@@ -735,7 +734,7 @@ class _CloudPlan:
             a.radii[i], a.nsamples[i], a.mlp[i] = float(sa.radii[i]), int(sa.nsamples[i]), mlps[i].data_ptr()
         scratch = {'idx': torch.empty(b, npoint, dtype=torch.int32, device=device),
                    'gpts': torch.empty(b, ng * gs, 4, device=device), 'gbox': torch.empty(b, ng, 8, device=device)}
-        if n <= 16384 and gs > 64 and ops.SLICE_BOXES:
+        if n <= 16384 and gs > 64:
             scratch['sbox'] = torch.empty(b, ng * (gs // 64), 8, device=device)
         need = lib.load().dclr_fps_workspace_bytes(b, n) if n > 16384 else 0
         if need:
@@ -888,8 +887,7 @@ class DeepCLR(BaseModel):
         sa = self._cloud_layers[0]
         sa0 = getattr(sa, '_sa0', None)
         if not self._rows_path or sa0 is None or getattr(sa, '_sa1', None) is not None or not sa0.fused or not x.is_cuda \
-                or x.shape[0] % 2 or x.shape[2] != self._input_dim or not x.is_contiguous() or x.dtype != torch.float32 \
-                or os.environ.get('DCLR_CLOUD_FUSED', '1') == '0':
+                or x.shape[0] % 2 or x.shape[2] != self._input_dim or not x.is_contiguous() or x.dtype != torch.float32:
             return None
         if ops.PRECISION == 'f16x2' and ops.CHECK_RANGE != 'never' and (
                 ops.CHECK_RANGE == 'always' or self._range_unchecked() or sa0.range_unchecked()):
@@ -942,7 +940,7 @@ class DeepCLR(BaseModel):
         sa = self._cloud_layers[0]
         sa0 = getattr(sa, '_sa0', None)
         if not self._rows_path or sa0 is None or getattr(sa, '_sa1', None) is not None or not sa0.fused or not x.is_cuda \
-                or x.shape[0] % 2 or x.shape[2] != self._input_dim or os.environ.get('DCLR_CLOUD_FUSED', '1') == '0':
+                or x.shape[0] % 2 or x.shape[2] != self._input_dim:
             return False
         per, nb, _ = view if view is not None else (x.shape[0] // 2, 1, 0)
         plan = self._cloud_plan(sa0, x, per, nb)
@@ -1054,8 +1052,7 @@ class DeepCLR(BaseModel):
 
     def _merge_plan(self, f_rows: torch.Tensor, pairs: int):
         flow, head = self._merge_layers[0], self._merge_layers[1]
-        if os.environ.get('DCLR_MERGE_FUSED', '1') == '0' or not isinstance(flow, MotionEmbedding) \
-                or not isinstance(head, OutputSimple) or not self._rows_path:
+        if not isinstance(flow, MotionEmbedding) or not isinstance(head, OutputSimple) or not self._rows_path:
             return None
         # the workspace belongs to one stream: calls enqueued on different streams may run side by side
         key = (f_rows.device, pairs, self.npoint, ops.PRECISION, ops.CHECK_RANGE == 'never', lib.stream_ptr())

@@ -34,7 +34,6 @@ PRECISION = os.environ.get('DCLR_PRECISION', 'f16x2')
 #                      two disagree or an activation leaves the range: a new checkpoint cannot clamp silently on first use;
 #   'always' (or '1')  every forward does (debugging; halves throughput);
 #   'never' (or '0')   no check.
-SLICE_BOXES = os.environ.get('DCLR_SLICE_BOXES', '1') != '0'    # A/B: 0 = set abstraction tests whole 256-point groups only
 CHECK_RANGE = {'1': 'always', '0': 'never'}.get(os.environ.get('DCLR_CHECK_RANGE', 'first'),
                                                 os.environ.get('DCLR_CHECK_RANGE', 'first'))
 if CHECK_RANGE not in ('first', 'always', 'never'):
@@ -256,7 +255,7 @@ def fps_clouds_grouped(clouds: torch.Tensor, npoint: int, view: Optional[Tuple[i
                   gbox.data_ptr(), lib.stream_ptr())
         return idx, gpts, gbox, None
     sbox = None
-    if n <= 16384 and gs > 64 and SLICE_BOXES:
+    if n <= 16384 and gs > 64:
         sbox = torch.empty(b, ng * (gs // 64), 8, dtype=torch.float32, device=clouds.device)
     need = lib.load().dclr_fps_workspace_bytes(b, n) if n > 16384 else 0
     ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=clouds.device) if need else None
@@ -426,7 +425,7 @@ def head_conv_fused_f16(x: torch.Tensor, k_in: int, layers, groups: int) -> torc
 
 def flow_f16_tile(k: int) -> int:
     """Tile width the library's split-f16 flow kernel wants its layer-2 / layer-3 weights packed with when it runs k
-    neighbours per point (32 from k = 29 up, 16 below; A/B builds force one)."""
+    neighbours per point (32 from k = 29 up, 16 below)."""
     return int(lib.load().dclr_flow_f16_tile(int(k)))
 
 

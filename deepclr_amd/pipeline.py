@@ -7,7 +7,6 @@ batches i+1 .. i+depth on side HIP streams while set abstraction, flow embedding
 of batch i run on the main stream (the reference never batches or pipelines: one pair per call,
 /root/reference/deepclr/models/base.py:118-120, scripts/inference.py:100-104).
 """
-import os
 from collections import deque
 from typing import Deque, Iterable, Iterator, Optional, Tuple
 
@@ -76,7 +75,7 @@ class PipelinedForward:
         self._eager = bool(eager_dense)
         if self._eager and not (dense_group and inputs_ready):
             raise ValueError("eager_dense needs dense_group and inputs_ready")
-        self._in_place = hasattr(model, '_cloud_layers') and os.environ.get('DCLR_BATCH_VIEW', '1') != '0'   # A/B: 0 = always concatenate
+        self._in_place = hasattr(model, '_cloud_layers')
         self._planned = False                       # launch plans of the side streams built (first _launch)
         self._hold_launch = False                   # dense groups: a full sampling group is launched right AFTER the next
                                                     # dense launch has been enqueued (the host needs ~0.3 ms for the chain)

@@ -1,4 +1,4 @@
-"""Flow-embedding kernel alone (k = 20, KITTI sizes; k = 30 ModelNet), HIP events; DCLR_FLOW_ABL selects timing-only ablations."""
+"""Flow-embedding kernel alone (k = 20, KITTI sizes; k = 30 ModelNet), HIP events."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

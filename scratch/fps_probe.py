@@ -1,5 +1,4 @@
-"""Sampler alone: time per launch and samples per barrier round (group_box[:, 0, 6]) on the bench clouds.
-Modes through the environment: default = per-group candidates, DCLR_FPS_WAVECAND=1, DCLR_FPS_SINGLE=1."""
+"""Sampler alone: time per launch and samples per barrier round (group_box[:, 0, 6]) on the bench clouds."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -354,20 +354,73 @@ def test_loss_values_match_reference_loss_modules():
         losses.transform_losses(y_pred * float('nan'), y, lt, 2)
 
 
-def test_hot_kernels_do_not_spill():
-    """The build records every kernel's registers / scratch (deepclr_amd/build.py): nothing on the hot path may use
-    scratch memory -- the 16384-point sampler once picked up 196 bytes of it from an innocent-looking epilogue and ran
-    20 % slower. Allowed: the A/B and fallback kernels that the default path never launches."""
+def test_no_kernel_spills():
+    """The build records every kernel's registers / scratch (deepclr_amd/build.py): no kernel may use scratch memory --
+    the 16384-point sampler once picked up 196 bytes of it from an innocent-looking epilogue and ran 20 % slower."""
     from deepclr_amd import build
     usage = build.kernel_usage()
     assert len(usage) >= 60, 'run python -m deepclr_amd.build'
     # (round 6: the sampler's fallback kernels fps_stream_kernel<32> / <64> -- no workspace, or hipMallocAsync refused --
     # no longer spill either: 252 / 904 bytes before)
-    single_sample_ab = re.compile(r'fps_paged_kernelILi\d+ELi0E')     # DCLR_FPS_SINGLE=1
-    spilled = {k: v['scratch'] for k, v in usage.items() if v['scratch'] and not single_sample_ab.search(k)}
+    spilled = {k: v['scratch'] for k, v in usage.items() if v['scratch']}
     assert not spilled, spilled
-    sampler = [v for k, v in usage.items() if 'fps_pruned_kernelILi1024ELi16ELi4ELi3E' in k]      # the table mode (default)
+    sampler = [v for k, v in usage.items() if _kernel_key(k) == ('fps_pruned_kernel', (1024, 16, 4))]
     assert sampler and sampler[0]['vgprs'] <= 128 and sampler[0]['occupancy'] >= 4      # 16 waves = one cloud per CU
+
+
+def _kernel_key(mangled):
+    """('name', (template arguments...)) of a mangled kernel name in the build's usage files (integer / bool literals)."""
+    m = re.match(r'_ZN12_GLOBAL__N_1(\d+)', mangled)
+    assert m, mangled
+    start = m.end()
+    name, rest = mangled[start:start + int(m.group(1))], mangled[start + int(m.group(1)):]
+    t = re.match(r'I((?:L[a-z]+\d+E)+)E', rest)
+    return name, tuple(int(a) for a in re.findall(r'L[a-z]+(\d+)E', t.group(1))) if t else ()
+
+
+# Every kernel the library compiles, keyed by name and template arguments, with the entry point that launches it.
+# A kernel that no entry point reaches does not belong in the build.
+_LAUNCHED_KERNELS = {
+    # dclr_fps_clouds*, dclr_furthest_point_sampling (fps.hip): 1024 < n <= 16384, <WGS, P, G> by n
+    ('fps_pruned_kernel', (512, 4, 4)), ('fps_pruned_kernel', (1024, 4, 4)), ('fps_pruned_kernel', (1024, 8, 4)),
+    ('fps_pruned_kernel', (1024, 16, 4)),
+    # dclr_fps_clouds_ws / _grouped_ws / _grouped_batched, dclr_furthest_point_sampling: 16384 < n <= 65536, <NG>
+    ('fps_paged_kernel', (8,)), ('fps_paged_kernel', (16,)),
+    # dclr_fps_clouds, dclr_furthest_point_sampling: n <= 1024
+    ('fps_reg_kernel', (1024, 1)),
+    # the same without a workspace (or hipMallocAsync refused): 16384 < n <= 65536 in registers, larger n over temp
+    ('fps_stream_kernel', (32,)), ('fps_stream_kernel', (64,)), ('fps_stream_kernel', (0,)),
+    # dclr_ball_query, dclr_gather_points, dclr_group_points, dclr_*_points_grad (grouping.hip)
+    ('ball_query_kernel', ()), ('gather_points_kernel', ()), ('group_points_kernel', ()), ('scatter_add_runs_kernel', ()),
+    # dclr_knn / dclr_knn_rows (knn.hip)
+    *(('knn_xyz_kernel', (p,)) for p in (1, 2, 4, 8, 16, 32, 64)),
+    *(('knn_rows_kernel', (p,)) for p in (1, 2, 4, 8, 16, 32, 64)),
+    # dclr_sa_msg_fused* (sa.hip) <scales, group-box chunks, f16, slice path>; dclr_rows_to_channels / _channels_to_rows
+    *(('sa_msg_kernel', (c, 1, f, sl)) for c in (3, 4) for f in (0, 1) for sl in (0, 1)),
+    *(('sa_msg_kernel', (c, 4, f, 0)) for c in (3, 4) for f in (0, 1)),
+    ('rows_to_channels_kernel', ()), ('channels_to_rows_kernel', ()),
+    # dclr_pack_weight*, dclr_linear / _linear_pair, dclr_head_conv_fused, dclr_fc (gemm.hip)
+    ('pack_weight_kernel', ()), ('pack_weight16_kernel', ()), ('linear_kernel', (1,)), ('linear_kernel', (2,)),
+    ('head_fused_kernel', ()), ('fc_kernel', ()),
+    # dclr_pack_weight_f16, dclr_head_conv_fused_f16 (gemm16.hip)
+    ('pack_weight_f16_kernel', ()), ('head16_kernel', (1,)), ('head16_kernel', (2,)),
+    # dclr_flow_embedding_fused (flow.hip): T = ceil(k / 4)
+    *(('flow_kernel', (t,)) for t in range(1, 9)),
+    # dclr_flow_embedding_fused_f16 (flow16.hip): 16-wide tiles up to k = 28, 32-wide tiles for k = 29..32
+    *(('flow16_kernel', (t,)) for t in range(1, 8)), ('flow32_kernel', (8,)),
+    # dclr_prepare_cloud* (prep.hip)
+    ('prep_count_kernel', ()), ('prep_scatter_kernel', ()),
+}
+
+
+def test_the_build_holds_exactly_the_launched_kernels():
+    """The library ships one form of each kernel: the set of compiled kernels equals the ones the entry points launch."""
+    from deepclr_amd import build
+    usage = build.kernel_usage()
+    assert len(usage) >= 60, 'run python -m deepclr_amd.build'
+    keys = [_kernel_key(k) for k in usage]
+    assert len(set(keys)) == len(keys)
+    assert set(keys) == _LAUNCHED_KERNELS
 
 
 def test_array_backed_input_dataflow_yields_the_reference_structure(tmp_path):
