@@ -1063,6 +1063,15 @@ extern "C" int dclr_sa_msg_fused_batched_ov(int f16, int b, int n, int c, int np
                      overflow);
 }
 
+extern "C" int dclr_sa_msg_fused_ov(int f16, int b, int n, int c, int npoint, const float *clouds, const int32_t *fps_idx,
+                                    int n_scales, const float *radii_host, const int *nsamples_host,
+                                    const float *const *mlp_host_ptrs, float *out_rows, int32_t *counts,
+                                    const float *group_pts, const float *group_box, const float *slice_box,
+                                    uint32_t *overflow, dclr_stream_t stream) {
+    return sa_launch(f16 != 0, b, n, c, npoint, clouds, fps_idx, n_scales, radii_host, nsamples_host, mlp_host_ptrs, out_rows,
+                     counts, group_pts, group_box, stream, DclrCloudView{0, 1, 0}, slice_box, overflow);
+}
+
 extern "C" int dclr_rows_to_channels(int b, int npoint, int nfeat, int xyz_col, int stride, const float *rows,
                                      float *channels, dclr_stream_t stream) {
     DCLR_REQUIRE(b > 0 && npoint > 0 && nfeat > 0 && xyz_col >= nfeat && stride >= xyz_col + 3 && rows &&

@@ -66,7 +66,8 @@ class ModelInferenceHelper:
         `predict` -- one pair per call, timed per call by the reference's scripts (scripts/timing.py:36-44) -- does not:
         a host-side wait behind every pair costs ~20 us of its 0.82 ms, so a caller of `predict` gets NaN poses from a
         clamped pair, the exception at the next call, or the exception here when it calls finish() after its last pair.
-        Models without such a check (the reference interface has none): a no-op."""
+        Set abstraction reports to the same word for any number of clouds: the single cloud of a sequential `predict`,
+        an odd frame count of `predict_sequence`. Models without such a check (the reference interface has none): a no-op."""
         check = getattr(self._model, 'check_range', None)
         if check is not None:
             check(synchronize='stream')

@@ -857,14 +857,24 @@ class DeepCLR(BaseModel):
                     fn()
 
     # -- row-level pipeline (what bench.py and the sharded runner drive) ---------------------------
+    def _refuse_off_rows(self, entry: str) -> None:
+        """The row-level entries serve the fused row pipeline only. A model that runs module by module (a `transform`
+        module, other layer widths, k or feature counts) has rows of another width or number per cloud -- the transform's
+        rows are not the feature module's -- and a pose computed from them would be silently wrong."""
+        if not self._rows_path:
+            raise NotImplementedError("{}: this model's configuration runs module by module, not on the fused row "
+                                      "pipeline; use forward() / ModelInferenceHelper.predict_batch".format(entry))
+
     def sample(self, x: torch.Tensor, view=None):
         """(2B, N, C) -> furthest-point sample (indices (2B, npoint) int32 + the kernel's spatial groups).
         view = ops.batch_view(batches): x is the first of several batches that are read where they lie; the result covers
         all of them in the order [templates of every batch | sources of every batch]."""
+        self._refuse_off_rows('sample')
         return self._cloud_layers[0].sample(x, view)
 
     def cloud_feature_rows(self, x: torch.Tensor, sample=None, view=None) -> torch.Tensor:
         """(2B, N, C) -> rows F ((2B)*npoint, 68); sample: precomputed self.sample(x), else computed here."""
+        self._refuse_off_rows('cloud_feature_rows')
         sa0 = getattr(self._cloud_layers[0], '_sa0', None)
         if sa0 is not None and x.is_cuda:
             sa0.overflow_ptr = self._range_flag_ptr()      # the split-f16 set-abstraction layers report a clamp there too
@@ -873,6 +883,7 @@ class DeepCLR(BaseModel):
     def merge_prep(self, f_rows: torch.Tensor, pairs: int):
         """The part of merge_rows that needs nothing but the feature rows (per-point halves of flow layer 1, kNN),
         for callers that run it ahead on another stream; None where the one-call path does not apply."""
+        self._refuse_off_rows('merge_prep')
         plan = self._merge_plan(f_rows, pairs)
         if plan is None:
             return None
@@ -884,9 +895,10 @@ class DeepCLR(BaseModel):
         prep), or None where the one-call path does not apply (a second set-abstraction level, shapes without a grouped
         sampler or a merge plan, the first -- range-checked -- forward after the weights changed): callers then take the
         two methods one after the other. The pipelined runner's sampling chain: ~0.3 ms of host time per launch otherwise."""
+        self._refuse_off_rows('cloud_merge_prep')
         sa = self._cloud_layers[0]
         sa0 = getattr(sa, '_sa0', None)
-        if not self._rows_path or sa0 is None or getattr(sa, '_sa1', None) is not None or not sa0.fused or not x.is_cuda \
+        if sa0 is None or getattr(sa, '_sa1', None) is not None or not sa0.fused or not x.is_cuda \
                 or x.shape[0] % 2 or x.shape[2] != self._input_dim or not x.is_contiguous() or x.dtype != torch.float32:
             return None
         if ops.PRECISION == 'f16x2' and ops.CHECK_RANGE != 'never' and (
@@ -954,6 +966,10 @@ class DeepCLR(BaseModel):
         """Rows F -> pose outputs (pairs, label_dim). Shapes the one-call path covers (MotionEmbedding +
         OutputSimple, fusable head) go through dclr_merge_forward: one foreign call and one allocation per batch
         instead of ten and a dozen -- at ~0.3 ms per step the host would otherwise set the pace."""
+        self._refuse_off_rows('merge_rows')
+        if f_rows.dim() != 2 or f_rows.shape[0] != 2 * pairs * self.npoint:
+            raise ValueError("merge_rows: rows F of shape {} for {} pairs; 2 * pairs * npoint = {} rows expected".format(
+                tuple(f_rows.shape), pairs, 2 * pairs * self.npoint))
         self._refuse_training_modules()
         self.check_range()
         if ops.PRECISION == 'f16x2' and ops.CHECK_RANGE != 'never' \
@@ -1072,6 +1088,9 @@ class DeepCLR(BaseModel):
         """Rows F of `frames` consecutive clouds (+ the rows of the frame before them, if any) -> the pair
         layout merge_rows() takes: templates = every frame but the last, sources = every frame but the first.
         Returns (rows, pairs, rows of the last frame)."""
+        if f_rows.dim() != 2 or f_rows.shape[0] != frames * self.npoint:
+            raise ValueError("sequence_rows: {} rows for {} frames of npoint = {}".format(tuple(f_rows.shape), frames,
+                                                                                       self.npoint))
         v = f_rows.view(frames, self.npoint, f_rows.shape[-1])
         if carry is not None:
             v = torch.cat((carry.view(1, self.npoint, -1), v))

@@ -65,6 +65,12 @@ class PipelinedForward:
             raise ValueError("ahead must be 'sample', 'features' or 'knn'")
         if group < 1 or (group > 1 and ahead == 'sample'):
             raise ValueError("group > 1 needs ahead='features' or 'knn'")
+        if not getattr(model, '_rows_path', True):
+            # a `transform` module, other layer widths, k or feature counts: the model runs module by module and has no
+            # rows F of the feature module to hand between the stages (DeepCLR.sample / cloud_feature_rows / merge_rows)
+            raise ValueError("this model's configuration runs module by module, not on the fused row pipeline the runner "
+                             "drives; use model.forward() / ModelInferenceHelper.predict_batch (predict_sequence for a "
+                             "sequence)")
         self._model = model.eval()
         model.prepare()                             # packed weights built here, on the caller's stream
         self.depth = depth
@@ -354,13 +360,24 @@ class PipelinedSequence(PipelinedForward):
     def __init__(self, model: DeepCLR, depth: int = 3, ahead: str = 'features', group: int = 1, dense_group: bool = False):
         if ahead == 'knn':
             raise ValueError("pairs straddle chunk borders: the kNN stage cannot run per chunk ahead of time")
+        if dense_group and (ahead != 'features' or group < 2):
+            raise ValueError("dense_group needs ahead='features' and group > 1")
         super().__init__(model, depth, ahead, group)
         self._carry: Optional[torch.Tensor] = None
-        self._seq_dense = bool(dense_group) and group > 1 and ahead == 'features'
+        self._seq_dense = bool(dense_group)
         self._seq_out = None                        # (chunks of the running dense group not yet stepped, outputs, their spans)
 
     def reset(self) -> None:
-        """Start a new sequence: no carried frame, and nothing left of a dense group whose chunks were not all stepped."""
+        """Start a new sequence: no carried frame, and nothing left of the old one -- neither a dense group whose chunks were
+        not all stepped, nor chunks sampled ahead or handed to prefetch() but never stepped (they would count as in flight
+        for good and hold back the prefetching of the new sequence). Their sampling launches may still run; their outputs
+        are dropped. `prefetched` stays the running total of chunks handed in (feeders difference it across a step)."""
+        for b in self._waiting:
+            b.__dict__.pop('_dclr_ready', None)          # never launched: nothing will wait for the event
+        self._waiting = []
+        self._pending.clear()
+        self._group_out = None
+        self._hold_launch = False
         self._carry = None
         self._seq_out = None
 

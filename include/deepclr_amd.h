@@ -287,6 +287,14 @@ int dclr_sa_msg_fused_batched_ov(int f16, int b, int n, int c, int npoint, const
                                  const float *radii_host, const int *nsamples_host, const float *const *mlp_host_ptrs,
                                  float *out_rows, int32_t *counts, const float *group_pts, const float *group_box,
                                  const float *slice_box, uint32_t *overflow, dclr_stream_t stream);
+/* dclr_sa_msg_fused (f16 == 0) / dclr_sa_msg_fused_f16 (f16 != 0) with the optional slice_box and the overflow word of
+ * dclr_sa_msg_fused_batched_ov, for ANY number of clouds b: the batched entries need b = 2 * pairs_per_batch * n_batches,
+ * and one cloud per call (sequential odometry) or an odd frame count is not that. ABI 0.2, added without a version change:
+ * nothing existing changed, a host finds the entry by its symbol. */
+int dclr_sa_msg_fused_ov(int f16, int b, int n, int c, int npoint, const float *clouds, const int32_t *fps_idx,
+                         int n_scales, const float *radii_host, const int *nsamples_host, const float *const *mlp_host_ptrs,
+                         float *out_rows, int32_t *counts, const float *group_pts, const float *group_box,
+                         const float *slice_box, uint32_t *overflow, dclr_stream_t stream);
 /* slice_box (optional, groups of more than 64 points, n <= 16384): (b, n_groups * group_size / 64, 8) f32, the boxes
  * (min xyz, max xyz, 0, 0) of the 64-point slices of every exported group -- a group's points are exported slice by slice,
  * slice r = the r-th 64 consecutive points of the spatially sorted cloud inside the group. Set abstraction tests a

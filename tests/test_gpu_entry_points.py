@@ -1,0 +1,448 @@
+"""GPU: every inference entry point on every golden model configuration; odd cloud counts and the activation-range word;
+PipelinedSequence.reset() and its options.
+
+test_gpu_model.py checks each golden configuration through model(x) / cloud_features only. The other routes to the same
+kernels -- the row-level API, PipelinedForward, PipelinedSequence, ModelInferenceHelper -- must give the same poses on
+every configuration, or refuse it with NotImplementedError / ValueError before any pose is out. Which (configuration,
+entry) pairs refuse is written down by hand below, not derived from a product flag: a new refusal fails like a wrong
+number does."""
+import types
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import oracle
+import oracle.model as oracle_model
+from deepclr_amd import lib, ops, synthetic
+from deepclr_amd.config import model_config_from_dict
+from deepclr_amd.labels import LabelType
+from deepclr_amd.models import build_model, ModelInferenceHelper
+from deepclr_amd.pipeline import PipelinedForward, PipelinedSequence
+from helpers import GOLDEN_CASES, load_golden, small_cfg
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+RTOL, ATOL = 1e-5, 1e-6                       # tests/test_gpu_model.py: activations against the fp32 CPU oracle
+POSE_ATOL = 1e-4                              # 4x4 pose, absolute
+
+# the shipped model families: every route is bit-identical to model(x) on the same pairs
+STANDARD = ('kitti_rand_n96_b2', 'kitti_n2048_b1', 'modelnet_n1024_b1')
+
+_ROWS = {'rows', 'rows+merge_prep', 'cloud_merge_prep', 'PipelinedForward', 'PipelinedSequence'}
+# (configuration -> entries that refuse). These configurations run module by module: the row pipeline has no rows F of
+# their feature module (other set-abstraction widths or input features; k = 70 in the flow embedding; a `transform`
+# module in front of the features, whose rows are the transform's). forward() and the helper serve them.
+REFUSES = {
+    'custom_widths_n512_b2': _ROWS,
+    'custom_features_n384_b2': _ROWS,
+    'small_k70_n512_b2': _ROWS,
+    'small_transform_n512_b2': _ROWS,
+}
+
+# (ahead, group, dense_group, dense_streams): test_pipelined_runner_matches_plain_forward's nine, plus dense streams
+RUNNER_SHAPES = [('sample', 1, False, 1), ('features', 1, False, 1), ('features', 2, False, 1), ('features', 3, False, 1),
+                 ('knn', 1, False, 1), ('knn', 2, False, 1), ('knn', 2, True, 1), ('knn', 3, True, 1), ('knn', 4, True, 1),
+                 ('knn', 1, False, 2), ('features', 1, False, 2)]
+
+
+def _models(cfg: dict, sd):
+    model = build_model(model_config_from_dict(cfg))
+    model.load_state_dict(sd, strict=True)
+    return model.to(DEV).eval(), oracle.build_oracle_model(cfg, sd)
+
+
+def _mats(y) -> np.ndarray:
+    return np.stack([LabelType.POSE3D_DUAL_QUAT.to_matrix(v) for v in np.asarray(y, dtype=np.float64)])
+
+
+def _mismatch(got, want_y, want_mat=None, exact=None):
+    """None if `got` (pairs, 8) matches want_y within RTOL / ATOL x scale, its 4x4 poses want_mat within POSE_ATOL and, where
+    `exact` is given, equals it bit for bit; otherwise what differs."""
+    if not torch.is_tensor(got):
+        return 'returned {!r}'.format(type(got).__name__)
+    got = got.detach().cpu()
+    want_y = torch.as_tensor(want_y, dtype=torch.float32)
+    if tuple(got.shape) != tuple(want_y.shape):
+        return 'shape {} != {}'.format(tuple(got.shape), tuple(want_y.shape))
+    if not bool(torch.isfinite(got).all()):
+        return 'non-finite pose outputs'
+    if not got.numel():
+        return None                                               # a sequence of one frame: no pair, no pose
+    scale = max(1.0, float(want_y.abs().max()))
+    err = float((got - want_y).abs().max())
+    if not torch.allclose(got, want_y, rtol=RTOL, atol=ATOL * scale):
+        return 'outputs off by {:.3g} (scale {:.3g})'.format(err, scale)
+    if got.shape[0]:
+        mat_err = float(np.abs(_mats(got.numpy()) - (_mats(want_y.numpy()) if want_mat is None else want_mat)).max())
+        if not mat_err < POSE_ATOL:
+            return '4x4 pose off by {:.3g}'.format(mat_err)
+    if exact is not None and not torch.equal(got, exact.detach().cpu()):
+        return 'not bit-identical to model(x) (max diff {:.3g})'.format(float((got - exact.detach().cpu()).abs().max()))
+    return None
+
+
+def _judge(problems, name, entry, fn, check):
+    """Run one entry: it must refuse (NotImplementedError / ValueError, no pose handed out) exactly where the table says
+    so, and otherwise pass `check(result)` (None = fine, else the complaint)."""
+    refuse = entry.split('[')[0] in REFUSES.get(name, ())
+    try:
+        got = fn()
+    except (NotImplementedError, ValueError) as e:
+        if not refuse:
+            problems.append('{} / {}: refused ({}: {})'.format(name, entry, type(e).__name__, e))
+        return
+    except Exception as e:                                        # noqa: BLE001 -- collected, the test fails below
+        problems.append('{} / {}: raised {}: {}'.format(name, entry, type(e).__name__, e))
+        return
+    if refuse:
+        problems.append('{} / {}: ran instead of refusing{}'.format(
+            name, entry, '' if check(got) is None else ' -- and its poses are wrong: ' + str(check(got))))
+        return
+    bad = check(got)
+    if bad is not None:
+        problems.append('{} / {}: {}'.format(name, entry, bad))
+
+
+@pytest.mark.parametrize('name', list(GOLDEN_CASES))
+def test_pairwise_entry_points_on_every_golden(name):
+    """The golden x = [templates | sources] of B pairs through the row API (with and without merge_prep, and the one-call
+    cloud_merge_prep), PipelinedForward in every shape on one-pair batches and on whole batches (group launches then see
+    several batches), and the helper's predict / predict_batch."""
+    g, cfg, sd = load_golden(name)
+    model, _ = _models(cfg, sd)
+    x = torch.from_numpy(g['x']).to(DEV)
+    b = x.shape[0] // 2
+    y_g, mat_g = g['y'], g['mat']
+    with torch.no_grad():
+        model(x.clone())                                          # the first, range-checked forward of the checkpoint
+        want = model(x.clone())[0]
+        singles = [x[[i % b, b + i % b]].contiguous() for i in range(3)]      # separate allocations, 3 batches even for B = 1
+        want_single = [model(s.clone())[0] for s in singles]
+    exact = name in STANDARD
+    problems = []
+
+    def check_all(got):
+        return _mismatch(got, y_g, mat_g, want if exact else None)
+
+    def row_api():
+        return model.merge_rows(model.cloud_feature_rows(x, model.sample(x)), b)
+
+    def row_api_prep():
+        rows = model.cloud_feature_rows(x, model.sample(x))
+        return model.merge_rows(rows, b, prep=model.merge_prep(rows, b))
+
+    def one_call():
+        got = model.cloud_merge_prep(x)
+        if got is None:                                           # the one-call path does not apply: the two methods
+            rows = model.cloud_feature_rows(x)
+            got = rows, model.merge_prep(rows, b)
+        return model.merge_rows(got[0], b, prep=got[1])
+
+    with torch.no_grad():
+        _judge(problems, name, 'rows', row_api, check_all)
+        _judge(problems, name, 'rows+merge_prep', row_api_prep, check_all)
+        _judge(problems, name, 'cloud_merge_prep', one_call, check_all)
+
+    def check_list(wants_y, wants_exact):
+        def check(outs):
+            if len(outs) != len(wants_y):
+                return '{} outputs for {} batches'.format(len(outs), len(wants_y))
+            for i, (o, wy, we) in enumerate(zip(outs, wants_y, wants_exact)):
+                bad = _mismatch(o, wy, None, we if exact else None)
+                if bad is not None:
+                    return 'batch {}: {}'.format(i, bad)
+            return None
+        return check
+
+    single_y = [y_g[[i % b]] for i in range(3)]
+    for ahead, group, dense, streams in RUNNER_SHAPES:
+        label = 'PipelinedForward[{}, group {}, dense_group {}, dense_streams {}]'.format(ahead, group, dense, streams)
+        for batches, wants_y, wants_exact in ((singles, single_y, want_single),
+                                              ([x.clone(), x.clone()], [y_g, y_g], [want, want])):
+            _judge(problems, name, label,
+                   lambda: [y.clone() for y in PipelinedForward(model, depth=2, ahead=ahead, group=group, dense_group=dense,
+                                                                dense_streams=streams).run(batches)],
+                   check_list(wants_y, wants_exact))
+    helper = ModelInferenceHelper(model)
+    for i in range(b):
+        _judge(problems, name, 'predict[pair {}]'.format(i), lambda: helper.predict(x[b + i], x[i]).unsqueeze(0),
+               lambda got: _mismatch(got, y_g[[i]], mat_g[[i]], want_single[i] if exact else None))
+    _judge(problems, name, 'predict_batch', lambda: helper.predict_batch(x[b:], x[:b]), check_all)
+    model.check_range(synchronize=True)
+    assert not problems, '\n'.join(problems)
+
+
+def _chunkings(t: int):
+    """Chunk lengths over t frames: 1, 3, 1, 3, ... / 2, 2, ... / all at once."""
+    out = []
+    for pattern in ((1, 3), (2,), (t,)):
+        lens, i = [], 0
+        while sum(lens) < t:
+            lens.append(min(pattern[i % len(pattern)], t - sum(lens)))
+            i += 1
+        if lens not in out:
+            out.append(lens)
+    return out
+
+
+@pytest.mark.parametrize('name', list(GOLDEN_CASES))
+def test_sequential_entry_points_on_every_golden(name):
+    """The golden's 2B clouds as consecutive frames, an even count (all of them) and an odd count (reversed, one dropped):
+    per-frame sequential predict, predict_sequence and PipelinedSequence (dense groups off, on with group 2 and 3) over
+    chunkings with chunks of 1 and 3 frames. Pose t = oracle(frame t-1 -> frame t), computed on this host."""
+    g, cfg, sd = load_golden(name)
+    model, orc = _models(cfg, sd)
+    x_h = torch.from_numpy(g['x'])
+    n_frames = x_h.shape[0]
+    problems = []
+    with torch.no_grad():
+        model(x_h.to(DEV))                                        # the first, range-checked forward of the checkpoint
+    for order in (list(range(n_frames)), list(range(n_frames - 1, 0, -1))):
+        frames_h = x_h[order].contiguous()
+        frames = frames_h.to(DEV)
+        t = frames.shape[0]
+        want = torch.cat([orc(torch.stack((frames_h[i - 1], frames_h[i]))) for i in range(1, t)]) if t > 1 \
+            else torch.zeros(0, 8)
+        tag = '{} frames'.format(t)
+
+        def seq_predict():
+            helper = ModelInferenceHelper(model, is_sequential=True)
+            outs = [helper.predict(frames[i]) for i in range(t)]
+            helper.finish()
+            if outs[0] is not None:
+                raise AssertionError('first frame of a sequence returned a pose')
+            return torch.stack(outs[1:]) if t > 1 else torch.zeros(0, 8)
+
+        _judge(problems, name, 'predict[{}]'.format(tag), seq_predict, lambda got: _mismatch(got, want))
+        for lens in _chunkings(t):
+            starts = np.cumsum([0] + lens)
+            chunks = [frames[a:e] for a, e in zip(starts[:-1], starts[1:])]
+
+            def seq_chunks():
+                helper = ModelInferenceHelper(model, is_sequential=True)
+                return torch.cat([helper.predict_sequence(c) for c in chunks])
+
+            _judge(problems, name, 'predict_sequence[{}, chunks {}]'.format(tag, lens), seq_chunks,
+                   lambda got: _mismatch(got, want))
+            for group, dense in ((1, False), (2, True), (3, True)):
+                def seq_runner():
+                    runner = PipelinedSequence(model, depth=2, group=group, dense_group=dense)
+                    outs = [y.clone() for y in runner.run(chunks)]
+                    model.check_range(synchronize=True)
+                    if [o.shape[0] for o in outs] != [c.shape[0] - (1 if i == 0 else 0) for i, c in enumerate(chunks)]:
+                        raise AssertionError('poses per chunk: {}'.format([o.shape[0] for o in outs]))
+                    return torch.cat(outs)
+
+                _judge(problems, name, 'PipelinedSequence[{}, chunks {}, group {}, dense_group {}]'.format(
+                    tag, lens, group, dense), seq_runner, lambda got: _mismatch(got, want))
+    assert not problems, '\n'.join(problems)
+
+
+# ---- odd cloud counts and the activation-range word ------------------------------------------------------------------
+def _sa_peaks(orc, x: torch.Tensor):
+    """Largest |pre-activation| of every layer of the oracle's forward over x, by state_dict key of the layer's weight."""
+    names = {id(v): k for k, v in orc.sd.items()}
+    peaks = {}
+
+    def wrap(fn):
+        def run(h, w, bias=None, *args, **kwargs):
+            y = fn(h, w, bias, *args, **kwargs)
+            key = names[id(w)]
+            peaks[key] = max(peaks.get(key, 0.0), float(y.abs().max()))
+            return y
+        return run
+
+    shim = types.SimpleNamespace(**{k: getattr(F, k) for k in dir(F) if not k.startswith('_')})
+    shim.conv2d, shim.conv1d, shim.linear = wrap(F.conv2d), wrap(F.conv1d), wrap(F.linear)
+    real, oracle_model.F = oracle_model.F, shim
+    try:
+        orc(x)
+    finally:
+        oracle_model.F = real
+    return peaks
+
+
+SA_SCALE = 15.0           # set-abstraction layer 2 weights x SA_SCALE, layer 3 / SA_SCALE
+HOT = 2.0e4               # intensities x HOT: layer 2's outputs pass 65504, nothing else comes near it
+
+
+def _range_model():
+    """small_cfg with set-abstraction layer 2 scaled up and layer 3 down: in-range clouds keep every activation far below
+    the split-f16 limit; clouds with HOT x larger intensities exceed it in set abstraction only (asserted on the oracle
+    by the test that uses it)."""
+    cfg = small_cfg()
+    sd = synthetic.random_state_dict(cfg, seed=5)
+    for s in range(2):
+        sd['_cloud_layers.0._sa0.mlps.%d.layer1.conv.weight' % s] = sd['_cloud_layers.0._sa0.mlps.%d.layer1.conv.weight' % s] * SA_SCALE
+        sd['_cloud_layers.0._sa0.mlps.%d.layer2.conv.weight' % s] = sd['_cloud_layers.0._sa0.mlps.%d.layer2.conv.weight' % s] / SA_SCALE
+    model, orc = _models(cfg, sd)
+    return model, orc
+
+
+def _hot(clouds: torch.Tensor) -> torch.Tensor:
+    hot = clouds.clone()
+    hot[..., 3] *= HOT
+    return hot
+
+
+def test_set_abstraction_reports_a_clamp_at_odd_cloud_counts():
+    """ops.sa_msg_fused with the range word at b = 1, 3, 5 (sequential odometry, odd frame counts): the word is set if and
+    only if an out-of-range cloud is in the call; rows and counts of the in-range clouds equal those of the same clouds in an
+    even, batched call and the oracle's sa_msg_forward; the f32 path gives the same results and never sets the word."""
+    cfg = small_cfg()
+    model, _ = _models(cfg, synthetic.random_state_dict(cfg, seed=6))
+    sam = model._cloud_layers[0]._sa0
+    mlps, npoint = sam.packed_mlps(), sam.npoint
+    cold_h = torch.from_numpy(synthetic.make_batch('kitti', 3, 2048, first_pair=40))        # 6 clouds
+    cold = cold_h.to(DEV)
+    hot = cold.clone()
+    hot[:, :, 3] *= 1.0e9                                             # set abstraction layer 1 leaves the f16 range
+    weights = [[(u.conv.weight.detach().cpu(), u.conv.bias.detach().cpu()) for u in stack] for stack in sam.mlps]
+    new_xyz_o, feat_o = oracle_model.sa_msg_forward(cold_h[:, :, :3].contiguous(), cold_h[:, :, 3:].transpose(1, 2).contiguous(),
+                                                    npoint, sam.radii, sam.nsamples, weights)
+    flag = lib.MappedFlag()
+
+    def call(clouds, precision):
+        fps, gpts, gbox, sbox = ops.fps_clouds_grouped(clouds, npoint)
+        groups = None if gpts is None else (gpts, gbox) + (() if sbox is None else (sbox,))
+        view = (clouds.shape[0] // 2, 1, 0) if clouds.shape[0] % 2 == 0 else None          # even: the batched entry
+        flag.clear()
+        rows, counts = ops.sa_msg_fused(clouds, fps, sam.radii, sam.nsamples, mlps, want_counts=True, groups=groups,
+                                        precision=precision, view=view, overflow=flag.dev_ptr)
+        torch.cuda.synchronize()
+        return fps, rows.view(clouds.shape[0], npoint, -1), counts, flag.is_set()
+
+    for precision in ('f16x2', 'f32'):
+        fps6, rows6, counts6, set6 = call(cold, precision)
+        assert not set6, precision
+        assert torch.equal(fps6.cpu(), oracle.furthest_point_sample(cold_h[:, :, :3].contiguous(), npoint))
+        for j in range(6):                                            # rows: 64 features | xyz at column 64
+            assert torch.equal(rows6[j, :, 64:67].cpu(), new_xyz_o[j])
+        torch.testing.assert_close(rows6[:, :, :64].cpu(), feat_o.transpose(1, 2), rtol=RTOL,
+                                   atol=ATOL * max(1.0, float(feat_o.abs().max())))
+        for b in (1, 3, 5):
+            for hot_at in (None, b // 2, b - 1):
+                clouds = cold[:b].clone()
+                if hot_at is not None:
+                    clouds[hot_at] = hot[hot_at]
+                fps, rows, counts, is_set = call(clouds, precision)
+                what = (precision, b, hot_at)
+                assert is_set == (hot_at is not None and precision == 'f16x2'), what
+                assert torch.equal(fps, fps6[:b]) and torch.equal(counts, counts6[:b]), what      # counts: xyz only
+                keep = [j for j in range(b) if j != hot_at]
+                assert torch.equal(rows[keep, :, :67], rows6[keep, :, :67]), what              # (column 67: padding)
+    assert not flag.is_set()
+
+
+def _check_silent_pose(run, model):
+    """`run()` must raise the range error, or return poses that are all NaN after which check_range raises."""
+    try:
+        y = run()
+    except RuntimeError as e:
+        assert 'DCLR_PRECISION=f32' in str(e), e
+        model.check_range(synchronize=True)                           # reported once, then cleared
+        return 'raised'
+    assert y is not None and y.numel() > 0
+    y = y.detach().cpu()
+    assert bool(torch.isnan(y).all()), 'a clamped forward handed out finite poses: {}'.format(y)
+    with pytest.raises(RuntimeError, match='DCLR_PRECISION=f32'):
+        model.check_range(synchronize=True)
+    return 'nan'
+
+
+def test_odd_cloud_counts_never_hand_out_a_clamped_pose_silently():
+    """Sequential predict (one cloud per call), predict_sequence over 3 frames and a PipelinedSequence chunk of 3 frames all
+    run set abstraction on an odd number of clouds. With a frame whose activations pass 65504 in set abstraction -- and
+    nowhere else, so that no later kernel reports it instead -- none of them may return a finite pose."""
+    model, orc = _range_model()
+    clouds_h = torch.from_numpy(synthetic.make_batch('kitti', 2, 2048, first_pair=3))        # 4 clouds
+    cold_h, hot_h = clouds_h, _hot(clouds_h)
+    # on the oracle: in range everywhere for the in-range clouds; for the hot ones beyond the limit in set abstraction
+    # layer 2 (the operands of layer 3) and at most a quarter of it after set abstraction
+    limit = ops.F16_MAX
+    for pair in ((0, 1), (1, 2), (2, 3)):
+        cold_p = _sa_peaks(orc, cold_h[list(pair)])
+        hot_p = _sa_peaks(orc, torch.stack((cold_h[pair[0]], hot_h[pair[1]])))
+        assert max(cold_p.values()) < limit / 100, cold_p
+        sa_l2 = [v for k, v in hot_p.items() if k.startswith('_cloud_layers.') and '.layer1.' in k]
+        after = [v for k, v in hot_p.items() if not k.startswith('_cloud_layers.')]
+        assert len(sa_l2) == 2 and max(sa_l2) > limit, hot_p
+        assert len(after) > 5 and max(after) < limit / 4, hot_p
+    cold, hot = cold_h.to(DEV), hot_h.to(DEV)
+    with torch.no_grad():
+        y_cold = model(cold.clone())[0]                               # the first, range-checked forward passes
+        assert bool(torch.isfinite(y_cold).all())
+    model.check_range(synchronize=True)
+    # sequential predict: the hot frame is the source of one pair
+    helper = ModelInferenceHelper(model, is_sequential=True)
+    assert helper.predict(cold[0]) is None
+    assert bool(torch.isfinite(helper.predict(cold[1]).cpu()).all())
+    helper.finish()
+
+    def hot_predict():
+        y = helper.predict(hot[2])
+        helper.finish()
+        return y
+    _check_silent_pose(hot_predict, model)
+    # predict_sequence over T = 3 frames (fresh state: two pairs)
+    seq = ModelInferenceHelper(model, is_sequential=True)
+    _check_silent_pose(lambda: seq.predict_sequence(torch.stack((cold[0], hot[1], cold[2]))), model)
+    # a PipelinedSequence chunk of 3 frames
+    runner = PipelinedSequence(model, depth=2)
+    _check_silent_pose(lambda: torch.cat([y.clone() for y in runner.run([torch.stack((cold[0], cold[1], hot[2]))])]), model)
+    # in range again: finite poses, nothing reported
+    with torch.no_grad():
+        y_again = model(cold.clone())[0]
+    model.check_range(synchronize=True)
+    assert _mismatch(y_again, y_cold.cpu()) is None
+
+
+# ---- PipelinedSequence: reset() and options --------------------------------------------------------------------------
+@pytest.mark.parametrize('dense', [False, True])
+def test_sequence_runner_reset_drops_the_old_sequence(monkeypatch, dense):
+    """reset() in the middle of a sequence -- one chunk of a sampling group of three stepped, another group sampled and not
+    stepped, one chunk handed to prefetch() and not launched -- must leave nothing of it: the next sequence's poses equal a
+    fresh helper's, every one of its chunks is sampled ahead on a side stream, and nothing is in flight at the end."""
+    cfg = synthetic.model_cfg('kitti')
+    model, _ = _models(cfg, synthetic.random_state_dict(cfg, seed=8))
+    seq_a = torch.from_numpy(synthetic.make_batch('kitti', 4, 2048, first_pair=60)).to(DEV)        # 8 frames
+    seq_b = torch.from_numpy(synthetic.make_batch('kitti', 3, 2048, first_pair=70)).to(DEV)        # 6 frames
+    with torch.no_grad():
+        model(seq_b[:2].clone())                                      # the first, range-checked forward of the checkpoint
+    want = ModelInferenceHelper(model, is_sequential=True).predict_sequence(seq_b)
+    main = torch.cuda.current_stream().cuda_stream
+    on_main = []
+    real = type(model).cloud_feature_rows
+    monkeypatch.setattr(type(model), 'cloud_feature_rows',
+                        lambda self, x, sample=None, view=None: on_main.append(torch.cuda.current_stream().cuda_stream == main)
+                        or real(self, x, sample, view))
+    runner = PipelinedSequence(model, depth=2, group=3, dense_group=dense)
+    a_chunks = [seq_a[i:i + 1] for i in range(7)]
+    for c in a_chunks[:6]:
+        runner.prefetch(c, flush=False)                               # two sampling launches of three chunks
+    runner.prefetch(a_chunks[6], flush=False)                         # waits for a group that never fills
+    assert runner.step(a_chunks[0]).shape[0] == 0                     # the first frame of a sequence: no pose
+    assert runner.in_flight() == 6
+    runner.reset()
+    assert runner.in_flight() == 0
+    on_main.clear()
+    b_chunks = [seq_b[i:i + 1] for i in range(6)]
+    got = torch.cat([y.clone() for y in runner.run(b_chunks)])
+    assert torch.equal(got, want)
+    assert runner.in_flight() == 0
+    assert on_main and not any(on_main), on_main                      # every chunk of the new sequence sampled ahead
+    model.check_range(synchronize=True)
+
+
+def test_sequence_runner_refuses_dense_groups_it_cannot_form():
+    """dense_group=True needs ahead='features' and group > 1 (PipelinedForward raises for its own invalid combinations
+    too); bench.py builds the sequence runner with dense_group only where group > 1."""
+    cfg = small_cfg()
+    model, _ = _models(cfg, synthetic.random_state_dict(cfg, seed=1))
+    for kwargs in ({'group': 1}, {'group': 0}, {'ahead': 'sample', 'group': 1}, {'ahead': 'sample', 'group': 2}):
+        with pytest.raises(ValueError):
+            PipelinedSequence(model, depth=2, dense_group=True, **kwargs)
+    assert PipelinedSequence(model, depth=2, group=2, dense_group=True)._seq_dense
+    assert not PipelinedSequence(model, depth=2, group=2)._seq_dense
