@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the DeepCLR forward hot path on MI355X: scan-pairs/s (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,15 +14,21 @@ exchange is an RCCL all-gather of the pose outputs.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (one fresh child process
 per GPU, before this process has touched the GPU) and relays rank 0's JSON line. Rank 0 prints ONE JSON line.
-The CPU oracle is used only for the `cpu_baseline` leg and the pose check -- never inside the timed region.
 `--steps K` is the number of timed steps; `ms_per_step` in the JSON line is the time of one of them. `--dump-outputs DIR`
 writes, after the timed window, the outputs of its last step (the (B, 8) poses a caller of the timed path receives) as
 DIR/y.npy (float32); inputs and weights are seeded, so the same arguments give the same inputs on every run.
 
-The plain single-GPU command (`python bench.py [--gpus 1 --steps K --warmup W]`, the driver's) measures the headline window first
-(a child process of its own) and then attaches a `secondary` block: steady state over 200 steps, --strict, ring scans, c4, c5 and
-the single-pair latency, each measured by a further child (pairs/s, ms/step, pose delta max, dominant kernel's roofline fraction);
-`--no-secondary` prints the headline alone. This parent process never touches the GPU.
+Without `--full` a run does what its headline needs and nothing more: set up, warm up, time the K steps, write the outputs
+if asked, print the line. Its per-kernel figures (`kernels_us`, `roofline`) are the HIP events of the timed window itself;
+the fields that take passes of their own stay null or absent.
+
+`--full` adds everything else, after the timed window: an untimed pass of the same launches one after another (`alone_us`,
+`frac_alone`, sampler rounds), the closed-loop latency pass, the pose check against the CPU oracle and the `cpu_baseline` leg
+(the CPU oracle is never used inside the timed region). The plain single-GPU command with `--full` (`python bench.py --full
+[--gpus 1 --steps K --warmup W]`) measures the headline window first (a child process of its own) and then attaches a
+`secondary` block: steady state over 200 steps, --strict, ring scans, c4, c5 and the single-pair latency, each measured by a
+further child (pairs/s, ms/step, pose delta max, dominant kernel's roofline fraction); `--no-secondary` prints the headline
+alone. That parent process never touches the GPU.
 
 Lines beside the headline (same schema, `config.mode` says which; profiles/r05_*):
   --strict    one batch of B pairs per sampling launch and per dense launch (no cross-batch fusion)
@@ -31,7 +37,8 @@ Lines beside the headline (same schema, `config.mode` says which; profiles/r05_*
   --clouds ring   LiDAR-density clouds (64 rings x azimuth, deepclr_amd/synthetic.py:ring_scan): ball queries reach
               their nsample caps, which the Gaussian clouds of the headline never do
   --latency   the reference's own call pattern: one pair per ModelInferenceHelper.predict call, per-pair ms between
-              events as /root/reference/scripts/timing.py:32-47 takes it (pairwise and sequential)
+              events as the reference's scripts/timing.py:32-47 takes it (pairwise; with --full also sequential,
+              back-to-back calls and per-kernel times)
 """
 import argparse
 import hashlib
@@ -482,10 +489,14 @@ def parse_args(argv=None):
                          '(0: every batch gets at least one pair; the secondary passes use a few pairs each)')
     ap.add_argument('--no-cpu-leg', action='store_true',
                     help='pose check against the oracle, but no cpu_baseline timing (the secondary passes)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed window also measure and check what the headline does not need: the untimed '
+                         'alone pass, the closed-loop latency pass, the pose check against the CPU oracle, cpu_baseline, and '
+                         'for the plain single-GPU c2 command the `secondary` block')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='the plain `bench.py [--gpus 1 --steps K --warmup W]` run prints the headline line only, without the '
-                         '`secondary` block (steady state, --strict, ring scans, c4, c5, single-pair latency measured by '
-                         'further child processes after the headline window)')
+                    help='the plain `bench.py --full [--gpus 1 --steps K --warmup W]` run prints the headline line only, '
+                         'without the `secondary` block (steady state, --strict, ring scans, c4, c5, single-pair latency '
+                         'measured by further child processes after the headline window)')
     ap.add_argument('--cpu-stub', action='store_true',
                     help='no GPU: gloo process group and a stand-in compute function (tests of the multi-rank plumbing)')
     ap.add_argument('--gather-every', type=int, default=None,
@@ -647,12 +658,13 @@ def pose_check(recent, cfg, sd, pairs_cfg: int, sequence: bool, budget_s: float,
 def run_latency(args, model, cfg, sd, kind, points, dev):
     """The reference's call pattern: ONE pair per call through ModelInferenceHelper.predict, timed as
     /root/reference/scripts/timing.py:32-47 does (events around predict, synchronize, per-pair ms; the clouds are on the
-    device before the first event, as there)."""
+    device before the first event, as there). The sequential leg, the back-to-back throughput and the per-kernel times are
+    --full only (None otherwise)."""
     from deepclr_amd.models import ModelInferenceHelper
     x = torch.from_numpy(synthetic.make_batch(kind, 1, points)).to(dev)
     out = {}
     iters = args.steps
-    for seq in (False, True):
+    for seq in ((False, True) if args.full else (False,)):
         helper = ModelInferenceHelper(model, is_sequential=seq)
         if seq:
             helper.predict(x[0])
@@ -671,6 +683,8 @@ def run_latency(args, model, cfg, sd, kind, points, dev):
             'mean_ms': sum(times) / len(times), 'calls': len(times)}
         if not seq:
             y_pair = y
+    if not args.full:
+        return out, y_pair, x, None, None
     # wall-clock throughput of back-to-back calls without a synchronize in between (what a caller that only needs the
     # poses at the end of a sequence gets)
     helper = ModelInferenceHelper(model, is_sequential=False)
@@ -754,7 +768,7 @@ def run(args):
                        'points_per_cloud': points, 'parallelism': 'dp1'},
             'latency_ms': lat, 'back_to_back_pairs_per_s': back_to_back, 'kernels_us': kernels, 'roofline': None,
         }
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             result['pose_delta_vs_oracle'] = pose_deltas(y.view(1, -1), x, cfg, sd, 1, False)[0]
             if not args.no_cpu_leg:
                 result['cpu_baseline'] = cpu_baseline(cfg, sd, cloud_kind, points)
@@ -1019,9 +1033,9 @@ def run(args):
         # this rank's block of the last all-gather (flushed by the closing fence) is what it sent: RCCL moved the bytes
         own_block_ok = bool(torch.equal(gather.gathered.view(world, -1)[rank], gather.send.view(-1)))
     alone, fps_rounds, latency = None, None, None
-    if rank == 0 and not stub and world == 1:
+    if args.full and rank == 0 and not stub and world == 1:
         latency = latency_pass((args.depth + 4) * args.group if args.group > 1 else 5 * args.depth + 10)   # > the batches in flight
-    if timer is not None and rank == 0:
+    if args.full and timer is not None and rank == 0:
         alone, fps_rounds = solo_pass(6)
     if use_dist:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -1161,7 +1175,7 @@ def run(args):
             result['traffic_source'] = traffic_src
         if kernels is not None:
             result['kernels_us'] = {k: round(v['avg_us'], 1) for k, v in sorted(kernels.items())}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # pose check of the last two launch groups of the timed loop against the oracle (outside the timed region), on
             # rank 0 at every world size (the metric's second half): every batch of them, as many pairs per batch as the
             # CPU budget allows. With an all-gather the outputs were written in place into its send buffer, which holds
@@ -1187,10 +1201,10 @@ def run(args):
 
 
 # ----------------------------------------------------------------------------------------------------------
-# secondary passes: `python bench.py [--gpus 1 --steps K --warmup W]` = headline window first, then the figures
+# secondary passes: `python bench.py --full [--gpus 1 --steps K --warmup W]` = headline window first, then the figures
 # DESIGN.md quotes beside it, each measured by a further child process and attached as `secondary`
 # ----------------------------------------------------------------------------------------------------------
-# name -> extra arguments of the child (each child also gets --no-secondary --no-cpu-leg and a small pose check)
+# name -> extra arguments of the child (each child also gets --full --no-secondary --no-cpu-leg and a small pose check)
 SECONDARY = (
     ('steady_200', ['--config', 'c2', '--steps', '200', '--warmup', '20', '--pose-pairs', '4']),
     ('strict', ['--config', 'c2', '--strict', '--steps', '200', '--warmup', '20', '--pose-pairs', '4']),
@@ -1211,7 +1225,7 @@ SECONDARY_TIMEOUT_S = 120            # per child; a child that fails or overruns
 HEADLINE_TIMEOUT_S = 600
 SECONDARY_DEADLINE_S = 420           # for ALL secondary passes together: past it the remaining ones are skipped (recorded as such),
                                      # so that headline + secondaries stay inside the driver's limit whatever hangs
-PLAIN_FLAGS = ('--gpus', '--steps', '--warmup', '--config', '--pose-budget', '--dump-outputs')
+PLAIN_FLAGS = ('--gpus', '--steps', '--warmup', '--config', '--pose-budget', '--dump-outputs', '--full')
 
 
 def under_profiler() -> bool:
@@ -1222,7 +1236,7 @@ def under_profiler() -> bool:
 
 
 def wants_secondary(args, argv) -> bool:
-    """The plain single-GPU c2 invocation (what the driver runs) and nothing else carries the secondary block."""
+    """The plain single-GPU c2 invocation and nothing else carries the secondary block (when it is run with --full)."""
     flags = [a for a in argv if a.startswith('--')]
     return (not under_profiler() and args.gpus == 1 and args.config == 'c2' and not args.no_secondary and 'WORLD_SIZE' not in os.environ
             and os.environ.get('DCLR_BENCH_CHILD') != '1' and all(f.split('=')[0] in PLAIN_FLAGS for f in flags))
@@ -1293,9 +1307,10 @@ def child_line(argv, timeout_s, run=None):
 
 
 def run_with_secondary(argv, run=None, plan=SECONDARY, out=sys.stdout, deadline_s=SECONDARY_DEADLINE_S, clock=time.time) -> int:
-    """Headline first (the unchanged window, a child of its own on the idle chip), then the secondary passes one after
-    another; ONE JSON line = the headline's with `secondary` attached. Any secondary failure is recorded in its slot; once
-    the passes together have used `deadline_s` the remaining ones are skipped, so the line is out in bounded time."""
+    """Headline first (the caller's --full arguments, the unchanged window, a child of its own on the idle chip), then the
+    secondary passes one after another; ONE JSON line = the headline's with `secondary` attached. Any secondary failure is
+    recorded in its slot; once the passes together have used `deadline_s` the remaining ones are skipped, so the line is out
+    in bounded time."""
     head, err = child_line(list(argv) + ['--no-secondary'], HEADLINE_TIMEOUT_S, run)
     if head is None:
         sys.stderr.write('bench.py: headline run failed: {}\n'.format(err))
@@ -1308,7 +1323,8 @@ def run_with_secondary(argv, run=None, plan=SECONDARY, out=sys.stdout, deadline_
         if left < 15:
             secondary[name] = {'error': 'skipped: the secondary passes had used their {} s'.format(deadline_s), 'args': ' '.join(extra)}
             continue
-        line, err = child_line(['--gpus', '1', '--no-secondary', '--no-cpu-leg'] + list(extra), min(SECONDARY_TIMEOUT_S, left), run)
+        line, err = child_line(['--gpus', '1', '--full', '--no-secondary', '--no-cpu-leg'] + list(extra), min(SECONDARY_TIMEOUT_S, left),
+                               run)
         secondary[name] = {'error': err, 'args': ' '.join(extra)} if line is None else dict(condense(line), args=' '.join(extra))
     secondary['note'] = ('each entry: a separate process after the headline window, same kernels and inputs policy (resident ring '
                          'of distinct batches), untimed for `value`; pose deltas against the CPU oracle on a few pairs each; '
@@ -1343,7 +1359,7 @@ def main(argv=None):
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # launched as `python bench.py --gpus N`: become the launcher (no GPU call has been made in this process)
         raise SystemExit(spawn_ranks(args.gpus, argv))
-    if wants_secondary(args, argv):
+    if args.full and wants_secondary(args, argv):
         # no GPU call has been made in this process and none will be: every measurement is a child
         raise SystemExit(run_with_secondary(argv))
     run(args)

@@ -194,13 +194,16 @@ def test_main_becomes_the_launcher_only_without_world_size(bench, monkeypatch):
     monkeypatch.delenv('DCLR_BENCH_CHILD', raising=False)
     bench.main(['--gpus', '1', '--no-secondary'])
     assert calls[-1] == ('run', 1)
-    # the plain single-GPU line (the driver's command) becomes the parent of the headline and secondary children
+    # the plain single-GPU line measures the headline in this process, with nothing attached
     monkeypatch.setattr(bench, 'run_with_secondary', lambda argv: calls.append(('secondary', list(argv))) or 0)
-    with pytest.raises(SystemExit) as e:
-        bench.main(['--gpus', '1', '--steps', '20', '--warmup', '5'])
-    assert e.value.code == 0 and calls[-1] == ('secondary', ['--gpus', '1', '--steps', '20', '--warmup', '5'])
-    monkeypatch.setenv('DCLR_BENCH_CHILD', '1')            # ... whose children run the measurement themselves
     bench.main(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert calls[-1] == ('run', 1)
+    # with --full it becomes the parent of the headline and secondary children
+    with pytest.raises(SystemExit) as e:
+        bench.main(['--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
+    assert e.value.code == 0 and calls[-1] == ('secondary', ['--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
+    monkeypatch.setenv('DCLR_BENCH_CHILD', '1')            # ... whose children run the measurement themselves
+    bench.main(['--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
     assert calls[-1] == ('run', 1)
 
 
@@ -303,6 +306,23 @@ def test_run_with_secondary_prints_one_line_with_every_pass_condensed(bench):
     assert res.returncode == 0 and res.stdout.strip() == '{}'
     # a failing headline is a failing run
     assert bench.run_with_secondary([], run=lambda *a, **k: types.SimpleNamespace(returncode=1, stdout=''), out=io.StringIO()) == 1
+
+
+def test_full_is_off_by_default_and_reaches_every_child(bench):
+    """A plain run does what its headline needs; --full (off by default) brings the passes and checks beside it, in the
+    headline child and in every secondary child alike."""
+    import io
+    import types
+    assert not bench.parse_args([]).full and bench.parse_args(['--full']).full
+    seen = []
+
+    def fake_run(cmd, env=None, stdout=None, text=None, timeout=None):
+        seen.append(cmd[2:])
+        return types.SimpleNamespace(returncode=0, stdout=json.dumps({'value': 1.0, 'unit': 'scan-pairs/s'}) + '\n')
+    argv = ['--gpus', '1', '--steps', '20', '--warmup', '5', '--full']
+    assert bench.run_with_secondary(argv, run=fake_run, out=io.StringIO()) == 0
+    assert seen[0] == argv + ['--no-secondary'] and len(seen) == 1 + len(bench.SECONDARY)
+    assert all(a.count('--full') == 1 for a in seen)
 
 
 def test_output_gather_bookkeeping_world_size_2(bench, tmp_path):
