@@ -129,13 +129,34 @@ __device__ __forceinline__ uint32_t dclr_lanemask_lt_popc(uint64_t mask) {
 // ---- batches that travel together without being concatenated (include/deepclr_amd.h, dclr_*_batched): the clouds of a
 // call are `batches` batches of 2 * per clouds each ([templates | sources], the reference's batch layout), batch i at
 // base + i * stride floats; the call numbers them [templates of every batch | sources of every batch]. batches <= 1: plain.
+// refs != NULL (dclr_*_ragged): cloud c is refs[c] instead -- its own base address and point count (dclr_cloud_ref).
 struct DclrCloudView {
     int per, batches;
     long long stride;
+    const DclrCloudRef *refs;
 };
 __device__ __forceinline__ size_t dclr_cloud_offset(const DclrCloudView &v, size_t c, size_t cloud_floats) {
     if (v.batches <= 1) return c * cloud_floats;
     const size_t half_n = (size_t)v.per * v.batches;        // templates (or sources) in the call
     const size_t half = c / half_n, r = c % half_n;
     return (r / v.per) * (size_t)v.stride + (half * v.per + r % v.per) * cloud_floats;
+}
+
+// Record c of a ragged call: the cloud's points; `n` receives its point count clamped to [1, n_cap] (the kernel's class
+// maximum, which sized every buffer the workgroup indexes). Read through the constant address space: the record is the
+// same for the whole workgroup (scalar loads, the count stays wave-uniform) and the kernels never write it.
+__device__ __forceinline__ const float *dclr_cloud_ref(const DclrCloudRef *refs, size_t c, int n_cap, int &n) {
+    typedef const uint32_t __attribute__((address_space(4))) *const_u32p;
+    const const_u32p r = (const_u32p)(refs + c);
+    const uint64_t lo = r[0], hi = r[1];
+    const int k = (int)r[2];
+    n = k < 1 ? 1 : k > n_cap ? n_cap : k;
+    return (const float *)((hi << 32) | lo);
+}
+// The same as an offset in floats from the kernel's own points argument `base` (the entry points pass the records'
+// address there), so that the kernel keeps indexing its argument: replacing the pointer instead cost the 16384-point
+// sampler 6 VGPRs and a spill. Records hold float arrays, so the distance is a whole number of floats.
+__device__ __forceinline__ long long dclr_cloud_ref_offset(const DclrCloudRef *refs, size_t c, const float *base, int n_cap,
+                                                           int &n) {
+    return ((long long)(intptr_t)dclr_cloud_ref(refs, c, n_cap, n) - (long long)(intptr_t)base) / (long long)sizeof(float);
 }

@@ -454,7 +454,8 @@ __global__ __launch_bounds__(WGS) void fps_pruned_kernel(int n, int pstride, int
     int32_t *picked = reinterpret_cast<int32_t *>(dyn_lds + BINS + NP / 2);   // shares storage with `cellof`
 
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    pts += dclr_cloud_offset(view, blockIdx.x, (size_t)n * pstride);
+    pts += view.refs ? dclr_cloud_ref_offset(view.refs, blockIdx.x, pts, NP, n)         // ragged call: this cloud's own
+                     : (long long)dclr_cloud_offset(view, blockIdx.x, (size_t)n * pstride);   // base and n
     const bool vec4 = pstride == 4 && ((uintptr_t)pts & 15) == 0;          // wave-uniform
     idx += (size_t)blockIdx.x * m;
     if (temp) temp += (size_t)blockIdx.x * n;
@@ -1122,7 +1123,8 @@ __global__ __launch_bounds__(1024) void fps_paged_kernel(int n, int pstride, int
     extern __shared__ int32_t picked[];
 
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    pts += dclr_cloud_offset(view, blockIdx.x, (size_t)n * pstride);
+    pts += view.refs ? dclr_cloud_ref_offset(view.refs, blockIdx.x, pts, NP, n)         // ragged call: this cloud's own
+                     : (long long)dclr_cloud_offset(view, blockIdx.x, (size_t)n * pstride);   // base and n
     const bool vec4 = pstride == 4 && ((uintptr_t)pts & 15) == 0;          // wave-uniform
     idx += (size_t)blockIdx.x * m;
     float4 *spts = spts_all + (size_t)blockIdx.x * NP;
@@ -1681,4 +1683,31 @@ extern "C" int dclr_fps_clouds_grouped_batched(int b, int n, int c, int m, const
     if (slice_box && gs <= 64) return DCLR_E_UNSUPPORTED;   // one slice per group: the group box is the slice box
     return fps_dispatch(b, n, c, m, clouds, nullptr, idx, (hipStream_t)stream, reinterpret_cast<float4 *>(group_pts),
                         group_box, view, slice_box);
+}
+
+// Clouds of different sizes in one launch (include/deepclr_amd.h, DclrCloudRef): the launch is that of b clouds of n_max
+// points -- n_max picks the instance and sizes every buffer -- and each workgroup reads its cloud's base and n from refs.
+extern "C" int dclr_fps_clouds_grouped_ragged(int b, int n_max, int c, int m, const DclrCloudRef *refs, int32_t *idx,
+                                              float *group_pts, float *group_box, float *slice_box, void *workspace,
+                                              long long workspace_bytes, dclr_stream_t stream) {
+    DCLR_REQUIRE(c >= 3 && b > 0 && m > 0 && refs && idx && group_pts && group_box);
+    DCLR_REQUIRE(((uintptr_t)refs & 7) == 0 && ((uintptr_t)group_pts & 15) == 0 && ((uintptr_t)group_box & 15) == 0);
+    int ng, gs;
+    if (!fps_group_layout(n_max, &ng, &gs)) return DCLR_E_UNSUPPORTED;
+    const DclrCloudView view{0, 1, 0, refs};
+    if (n_max > 16384) {
+        if (slice_box) return DCLR_E_UNSUPPORTED;           // the workspace kernel exports no slice boxes
+        if ((size_t)m * sizeof(int32_t) > 32 * 1024) return DCLR_E_UNSUPPORTED;
+        const size_t np = n_max <= 32768 ? 32768 : 65536;
+        DCLR_REQUIRE(workspace && workspace_bytes >= (long long)((size_t)b * np * 10) && ((uintptr_t)workspace & 15) == 0);
+        return fps_launch_paged(b, n_max, c, m, reinterpret_cast<const float *>(refs), idx, reinterpret_cast<float4 *>(group_pts),
+                                static_cast<char *>(workspace), group_box, nullptr, (hipStream_t)stream, view);
+    }
+    if (slice_box) {
+        if (gs <= 64) return DCLR_E_UNSUPPORTED;            // one slice per group: the group box is the slice box
+        DCLR_REQUIRE(((uintptr_t)slice_box & 15) == 0);
+    }
+    // (the records' address stands in for the points argument: the kernels add each cloud's offset from it)
+    return fps_dispatch(b, n_max, c, m, reinterpret_cast<const float *>(refs), nullptr, idx, (hipStream_t)stream,
+                        reinterpret_cast<float4 *>(group_pts), group_box, view, slice_box);
 }

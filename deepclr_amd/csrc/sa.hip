@@ -318,7 +318,9 @@ __global__ __launch_bounds__(SA_WAVES * 64, 4) void sa_msg_kernel(SaParams prm,
         bx = (int)(i % gridDim.x);
     }
     const int j0 = (bx * SA_WAVES + wave) * SA_CPW;                  // this wave's first centroid
-    const float *cloud = dclr_uniform(clouds + dclr_cloud_offset(prm.view, bi, (size_t)prm.n * C));   // scalar registers
+    int n_cloud = prm.n;                                             // ragged call (view.refs): this cloud's own n
+    const float *cloud = dclr_uniform(clouds + (prm.view.refs ? dclr_cloud_ref_offset(prm.view.refs, bi, clouds, prm.n, n_cloud)
+                                                              : (long long)dclr_cloud_offset(prm.view, bi, (size_t)prm.n * C)));   // scalar registers
 
     // The workgroup's 16 centroids go to LDS once. Without groups (exhaustive sweep) wave w keeps centroids 4 w .. 4 w + 3
     // for the whole kernel; with groups the waves PULL centroids one at a time (sa_next): a workgroup lives as long as its
@@ -869,14 +871,14 @@ __global__ __launch_bounds__(SA_WAVES * 64, 4) void sa_msg_kernel(SaParams prm,
             const int src = wave * SA_CPW + c;
             ccx[c] = sa_c16[src][0]; ccy[c] = sa_c16[src][1]; ccz[c] = sa_c16[src][2];
         }
-        const int n_tiles = (prm.n + SA_TILE - 1) / SA_TILE;
+        const int n_tiles = (n_cloud + SA_TILE - 1) / SA_TILE;
         constexpr int PER_THREAD = SA_TILE / (SA_WAVES * 64);           // points staged per thread
         float4 stage[PER_THREAD];
         auto fetch = [&](int t) {
 #pragma unroll
             for (int u = 0; u < PER_THREAD; ++u) {
                 const int k = t * SA_TILE + u * (SA_WAVES * 64) + tid;
-                stage[u] = k < prm.n ? sa_load_point<C>(cloud, k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                stage[u] = k < n_cloud ? sa_load_point<C>(cloud, k) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         };
         auto stash = [&](int buf) {
@@ -892,7 +894,7 @@ __global__ __launch_bounds__(SA_WAVES * 64, 4) void sa_msg_kernel(SaParams prm,
             for (int it = 0; it < SA_TILE / 64; ++it) {
                 const int k = t * SA_TILE + it * 64 + lane;
                 const float4 p = sa_tile[buf][it * 64 + lane];
-                const bool inb = k < prm.n;
+                const bool inb = k < n_cloud;
                 float d2c[SA_CPW];
 #pragma unroll
                 for (int c = 0; c < SA_CPW; ++c) d2c[c] = dclr_sqdist(ccx[c], ccy[c], ccz[c], p.x, p.y, p.z);
@@ -1070,6 +1072,22 @@ extern "C" int dclr_sa_msg_fused_ov(int f16, int b, int n, int c, int npoint, co
                                     uint32_t *overflow, dclr_stream_t stream) {
     return sa_launch(f16 != 0, b, n, c, npoint, clouds, fps_idx, n_scales, radii_host, nsamples_host, mlp_host_ptrs, out_rows,
                      counts, group_pts, group_box, stream, DclrCloudView{0, 1, 0}, slice_box, overflow);
+}
+
+// Clouds of different sizes (include/deepclr_amd.h, DclrCloudRef): n_max names the class, whose group layout the sampler
+// exported; the records give each workgroup its cloud.
+extern "C" int dclr_sa_msg_fused_ragged(int f16, int b, int n_max, int c, int npoint, const DclrCloudRef *refs,
+                                        const int32_t *fps_idx, int n_scales, const float *radii_host,
+                                        const int *nsamples_host, const float *const *mlp_host_ptrs, float *out_rows,
+                                        int32_t *counts, const float *group_pts, const float *group_box,
+                                        const float *slice_box, uint32_t *overflow, dclr_stream_t stream) {
+    DCLR_REQUIRE(refs && ((uintptr_t)refs & 7) == 0 && group_pts && group_box);
+    int ng, gs;
+    if (dclr_fps_group_layout(n_max, &ng, &gs) != DCLR_OK) return DCLR_E_UNSUPPORTED;
+    // the class maximum (= the sampler's padded cloud) bounds every record's n, as in the sampler
+    // (the records' address stands in for the clouds argument: the kernel adds each cloud's offset from it)
+    return sa_launch(f16 != 0, b, ng * gs, c, npoint, reinterpret_cast<const float *>(refs), fps_idx, n_scales, radii_host, nsamples_host, mlp_host_ptrs,
+                     out_rows, counts, group_pts, group_box, stream, DclrCloudView{0, 1, 0, refs}, slice_box, overflow);
 }
 
 extern "C" int dclr_rows_to_channels(int b, int npoint, int nfeat, int xyz_col, int stride, const float *rows,

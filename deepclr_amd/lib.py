@@ -39,6 +39,8 @@ SIGNATURES = {
     'dclr_sa_msg_fused_batched': [_i, _i, _i, _i, _i, _p, _i, _i, ctypes.c_longlong, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     'dclr_sa_msg_fused_batched_ov': [_i, _i, _i, _i, _i, _p, _i, _i, ctypes.c_longlong, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     'dclr_sa_msg_fused_ov': [_i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    'dclr_fps_clouds_grouped_ragged': [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, ctypes.c_longlong, _p],
+    'dclr_sa_msg_fused_ragged': [_i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     'dclr_rows_to_channels': [_i, _i, _i, _i, _i, _p, _p, _p],
     'dclr_channels_to_rows': [_i, _i, _i, _i, _i, _p, _p, _p],
     'dclr_pack_weight': [_i, _i, _p, _p, _i, _i, _p, _p],
@@ -100,6 +102,11 @@ class CloudArgs(ctypes.Structure):
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
         self.struct_size = ctypes.sizeof(type(self))
+
+
+class CloudRef(ctypes.Structure):
+    """DclrCloudRef (include/deepclr_amd.h): one cloud of a ragged call."""
+    _fields_ = [('pts', _p), ('n', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
 _lib: Optional[ctypes.CDLL] = None

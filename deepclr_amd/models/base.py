@@ -105,8 +105,31 @@ class ModelInferenceHelper:
             y, _, _ = self._model.forward(self.stack(template, source), is_feat=False)
             return y[0, :]
 
-    def predict_batch(self, sources: torch.Tensor, templates: torch.Tensor) -> torch.Tensor:
-        """sources / templates: (B, N, C) equally sized clouds -> (B, label_dim)."""
+    def _fit_list(self, clouds, which: str) -> list:
+        """A list of (N_i, C) clouds -> the same clouds' first input_dim columns (checked on the host only)."""
+        if not isinstance(clouds, (list, tuple)) or not clouds:
+            raise ValueError("expected a non-empty list of (N_i, C) {} clouds".format(which))
+        if any(not torch.is_tensor(c) or c.dim() != 2 for c in clouds):
+            raise ValueError("every {} cloud must be a 2-D (N, C) tensor".format(which))
+        if any(c.shape[1] < self._input_dim for c in clouds):
+            raise RuntimeError("Wrong point dimension in {}.".format(which))
+        return [c[:, :self._input_dim] for c in clouds]
+
+    def predict_batch(self, sources, templates) -> torch.Tensor:
+        """sources / templates: (B, N, C) equally sized clouds -> (B, label_dim).
+        Or two equally long lists of (N_i, C) clouds, sizes free (also between the template and the source of a pair):
+        pose i comes from the features of the full clouds t_i and s_i -- forward(cat(cloud_features([t_i]),
+        cloud_features([s_i])), is_feat=True) -- computed in one launch pair per size class. (predict() would instead
+        subsample the larger cloud of a pair at random to the smaller one's size, stack().)"""
+        if isinstance(sources, (list, tuple)) or isinstance(templates, (list, tuple)):
+            sources, templates = self._fit_list(sources, 'source'), self._fit_list(templates, 'template')
+            if len(sources) != len(templates):
+                raise RuntimeError("Batched prediction needs as many templates as sources.")
+            with torch.no_grad():
+                feats = self._model.cloud_features(templates + sources)
+                y, _, _ = self._model.forward(feats, is_feat=True)
+            self.finish()
+            return y
         if sources.shape != templates.shape:
             raise RuntimeError("Batched prediction needs equally shaped source and template batches.")
         if sources.shape[2] < self._input_dim:
@@ -117,16 +140,21 @@ class ModelInferenceHelper:
         self.finish()
         return y
 
-    def predict_sequence(self, frames: torch.Tensor) -> torch.Tensor:
+    def predict_sequence(self, frames) -> torch.Tensor:
         """Sequential mode over a chunk of consecutive frames (T, N, C): the same poses T calls of
         predict(frame) return (the first being None on a fresh state), with every frame's features computed
-        once and in one batch. Returns (T, label_dim), or (T-1, label_dim) when no frame was cached."""
+        once and in one batch. Returns (T, label_dim), or (T-1, label_dim) when no frame was cached.
+        frames may also be a list of T (N_i, C) frames of different sizes (one launch pair per size class); lists and
+        tensors may alternate between calls."""
         if not self._is_sequential:
             raise RuntimeError("predict_sequence needs a sequential helper.")
-        if frames.shape[2] < self._input_dim:
+        ragged = isinstance(frames, (list, tuple))
+        if ragged:
+            frames = self._fit_list(frames, 'source')
+        elif frames.shape[2] < self._input_dim:
             raise RuntimeError("Wrong point dimension in source.")
         with torch.no_grad():
-            feats = self._model.cloud_features(frames[:, :, :self._input_dim].contiguous())
+            feats = self._model.cloud_features(frames if ragged else frames[:, :, :self._input_dim].contiguous())
             if self._state is not None:
                 feats = torch.cat((self._state.unsqueeze(0), feats))
             self._state = feats[-1]

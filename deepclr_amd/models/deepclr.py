@@ -94,13 +94,24 @@ class SetAbstraction(DeepCLRModule):
 
     def forward_rows(self, clouds: torch.Tensor, sample=None, view=None) -> torch.Tensor:
         """(2B, N, C) point-major clouds -> rows F."""
+        self._refuse_off_rows()
+        rows = self._sa0.forward_rows(clouds, sample, view)
+        return self._second_level(rows, clouds.shape[0] if view is None else 2 * view[0] * view[1])
+
+    def forward_rows_ragged(self, clouds: List[torch.Tensor]) -> torch.Tensor:
+        """A list of (N_i, C) point-major clouds of different sizes -> rows F in list order (one launch pair per size class,
+        PointnetSAModuleMSG.forward_rows_ragged)."""
+        self._refuse_off_rows()
+        return self._second_level(self._sa0.forward_rows_ragged(clouds), len(clouds))
+
+    def _refuse_off_rows(self) -> None:
         if not self.rows_path:
             raise NotImplementedError("this set-abstraction shape runs composed (forward()); the row pipeline needs level 0 "
                                       "as xyz + <= 1 feature with mlp widths [16, 16, 32] and <= 64 output features")
-        rows = self._sa0.forward_rows(clouds, sample, view)
+
+    def _second_level(self, rows: torch.Tensor, b: int) -> torch.Tensor:
         if self._sa1 is None:
             return rows
-        b = clouds.shape[0] if view is None else 2 * view[0] * view[1]
         ch = ops.rows_to_channels(rows, b, self._sa0.npoint, self._sa0.out_features())
         xyz, feat = self._sa1(ch[:, :3, :].transpose(1, 2).contiguous(), ch[:, 3:, :].contiguous())
         return ops.channels_to_rows(torch.cat((xyz.transpose(1, 2), feat), dim=1).contiguous(), ops.F_STRIDE)
@@ -872,12 +883,21 @@ class DeepCLR(BaseModel):
         self._refuse_off_rows('sample')
         return self._cloud_layers[0].sample(x, view)
 
-    def cloud_feature_rows(self, x: torch.Tensor, sample=None, view=None) -> torch.Tensor:
-        """(2B, N, C) -> rows F ((2B)*npoint, 68); sample: precomputed self.sample(x), else computed here."""
+    def cloud_feature_rows(self, x, sample=None, view=None) -> torch.Tensor:
+        """(2B, N, C) -> rows F ((2B)*npoint, 68); sample: precomputed self.sample(x), else computed here.
+        x may also be a list of (N_i, C) clouds of different sizes (rows in list order; no sample or view): each size class
+        runs as one sampler and one set-abstraction launch, with the rows each cloud gets alone."""
         self._refuse_off_rows('cloud_feature_rows')
+        ragged = isinstance(x, (list, tuple))
+        if ragged:
+            if sample is not None or view is not None:
+                raise ValueError("cloud_feature_rows: a list of clouds takes neither `sample` nor `view`")
+            ops.check_cloud_list(x)
         sa0 = getattr(self._cloud_layers[0], '_sa0', None)
-        if sa0 is not None and x.is_cuda:
+        if sa0 is not None and (x[0] if ragged else x).is_cuda:
             sa0.overflow_ptr = self._range_flag_ptr()      # the split-f16 set-abstraction layers report a clamp there too
+        if ragged:
+            return self._cloud_layers[0].forward_rows_ragged(list(x))
         return self._cloud_layers[0].forward_rows(x, sample, view)
 
     def merge_prep(self, f_rows: torch.Tensor, pairs: int):
@@ -1105,8 +1125,19 @@ class DeepCLR(BaseModel):
         pts = x[:, :, :dim]
         x[:, :, :dim] = torch.baddbmm(m[:, :dim, dim].unsqueeze(1), pts, m[:, :dim, :dim].transpose(1, 2))
 
-    def cloud_features(self, x: torch.Tensor, m: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """(2B, N, C) -> (2B, 3 + feat, npoint) in the reference's channel-major layout."""
+    def cloud_features(self, x, m: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(2B, N, C) -> (2B, 3 + feat, npoint) in the reference's channel-major layout. x may also be a list of (N_i, C)
+        clouds of different sizes (m: one matrix per cloud): on the row pipeline one launch pair per size class
+        (cloud_feature_rows), otherwise cloud by cloud."""
+        if isinstance(x, (list, tuple)):
+            ops.check_cloud_list(x)
+            if m is not None:
+                for i, cloud in enumerate(x):
+                    self._augment(cloud.unsqueeze(0), m[i:i + 1])
+            if not self._rows_path:
+                return torch.cat([self.cloud_features(cloud.unsqueeze(0)) for cloud in x])
+            rows = self.cloud_feature_rows(list(x))
+            return ops.rows_to_channels(rows, len(x), self.npoint, self._cloud_layers[0].output_dim() - 3)
         if m is not None:
             self._augment(x, m)
         if not self._rows_path:                       # reference: x.transpose(1, 2) -> cloud layers (deepclr.py:516-520)

@@ -323,6 +323,128 @@ def sa_msg_fused(clouds: torch.Tensor, fps_idx: torch.Tensor, radii: Sequence[fl
     return (out, counts) if want_counts else out
 
 
+# Size classes of the ragged launches: (1024, 2048], (2048, 4096], ..., (32768, 65536] -- one kernel instance and group
+# layout each (fps_group_layout); every buffer of a launch is sized by its class maximum.
+RAGGED_CLASSES = (2048, 4096, 8192, 16384, 32768, 65536)
+
+
+def ragged_class(n: int, npoint: int = 1) -> Optional[int]:
+    """Largest point count of the size class a cloud of n points joins in a ragged launch, or None: n <= 1024 or
+    n > 65536 (no grouped sampler), or npoint beyond the class's sample buffer in LDS -- such clouds take the per-cloud
+    calls."""
+    if n <= 1024 or n > FUSED_MAX_POINTS or npoint * 4 > (32 if n > 16384 else 64) * 1024:
+        return None
+    return next(c for c in RAGGED_CLASSES if n <= c)
+
+
+def check_cloud_list(clouds) -> Tuple[torch.device, int]:
+    """Host-side validation of a list of (N_i, C) clouds (nothing touches the device): (device, C)."""
+    if not isinstance(clouds, (list, tuple)) or not clouds:
+        raise ValueError("expected a non-empty list of (N_i, C) clouds")
+    first = clouds[0]
+    for i, x in enumerate(clouds):
+        if not torch.is_tensor(x) or x.dim() != 2:
+            raise ValueError("cloud {}: expected a 2-D (N, C) tensor, got {}".format(
+                i, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+        if not x.is_cuda:
+            raise RuntimeError("cloud {} must be a GPU tensor (deepclr_amd has no CPU path)".format(i))
+        if x.dtype != torch.float32:
+            raise RuntimeError("cloud {} must be float32".format(i))
+        if x.device != first.device:
+            raise ValueError("cloud {} is on {}, cloud 0 on {}".format(i, x.device, first.device))
+        if x.shape[1] != first.shape[1] or x.shape[1] < 3:
+            raise ValueError("cloud {}: {} columns; every cloud needs the same number, at least 3 (cloud 0: {})".format(
+                i, x.shape[1], first.shape[1]))
+        if x.shape[0] < 1:
+            raise ValueError("cloud {} has no points".format(i))
+    return first.device, first.shape[1]
+
+
+def cloud_rows_ragged(clouds: Sequence[torch.Tensor], npoint: int, radii: Sequence[float], nsamples: Sequence[int],
+                      mlps: List[torch.Tensor], precision: Optional[str] = None, overflow: Optional[int] = None,
+                      single=None, want_counts: bool = False):
+    """Sampling + set abstraction of clouds of DIFFERENT sizes: a list of B (N_i, C) GPU tensors -> rows F
+    (B*npoint, 68) in input order [, idx (B, npoint) int32, counts (B, npoint, scales) with want_counts].
+    The clouds of each size class (RAGGED_CLASSES) go through one sampler launch and one set-abstraction launch
+    (dclr_fps_clouds_grouped_ragged / dclr_sa_msg_fused_ragged: per-cloud records, read where the clouds lie); a cloud
+    gets exactly the samples, rows and counts it gets alone. Clouds outside the classes take the per-cloud calls:
+    `single((1, N, C)) -> rows` where given (the module's own forward_rows, which also covers N > 65536), else the fused
+    calls (N <= 65536). precision / overflow: as sa_msg_fused."""
+    device, c = check_cloud_list(clouds)
+    b = len(clouds)
+    classes = [ragged_class(x.shape[0], npoint) for x in clouds]
+    if (single is None or want_counts) and any(x.shape[0] > FUSED_MAX_POINTS for x in clouds):
+        raise RuntimeError("clouds of more than {} points need the composed set abstraction (pass `single`; no counts)"
+                           .format(FUSED_MAX_POINTS))
+    clouds = [x.contiguous() for x in clouds]
+    # launch order: class by class (ascending), then the per-cloud rest; stable in the input order
+    order = sorted(range(b), key=lambda i: (classes[i] is None, classes[i] or 0, i))
+    identity = order == list(range(b))
+    n_ragged = sum(cl is not None for cl in classes)
+    # one pinned host buffer, one copy: the records (pts, n | reserved = 0) of the ragged clouds in launch order, then
+    # (only when the launch order is not the input order) the input position of every launched cloud
+    recs = torch.empty(2 * n_ragged + (0 if identity else b), dtype=torch.int64, pin_memory=True)
+    rv = recs.numpy()
+    for k, i in enumerate(order[:n_ragged]):
+        rv[2 * k], rv[2 * k + 1] = clouds[i].data_ptr(), clouds[i].shape[0]
+    if not identity:
+        rv[2 * n_ragged:] = order
+    dev = recs.to(device, non_blocking=True) if recs.numel() else None
+    ns = len(radii)
+    rows = torch.empty(b * npoint, F_STRIDE, dtype=torch.float32, device=device)
+    out_rows = rows if identity else torch.empty_like(rows)            # launch order
+    idx_all = torch.empty(b, npoint, dtype=torch.int32, device=device) if want_counts else None
+    cnt_all = torch.empty(b, npoint, ns, dtype=torch.int32, device=device) if want_counts else None
+    radii_h = (ctypes.c_float * ns)(*[float(r) for r in radii])
+    nsamp_h = (ctypes.c_int * ns)(*[int(s) for s in nsamples])
+    mlp_h = (ctypes.c_void_p * ns)(*[lib.dev_f32(m, 'mlp').data_ptr() for m in mlps])
+    f16 = int((precision or PRECISION) == 'f16x2')
+    k = 0
+    while k < n_ragged:
+        cls = classes[order[k]]
+        e = k
+        while e < n_ragged and classes[order[e]] == cls:
+            e += 1
+        nb = e - k
+        ng, gs = fps_group_layout(cls)
+        refs = dev.data_ptr() + 16 * k
+        idx = idx_all[k:e] if want_counts else torch.empty(nb, npoint, dtype=torch.int32, device=device)
+        gpts = torch.empty(nb, ng * gs, 4, dtype=torch.float32, device=device)
+        gbox = torch.empty(nb, ng, 8, dtype=torch.float32, device=device)
+        sbox = torch.empty(nb, ng * (gs // 64), 8, dtype=torch.float32, device=device) if cls <= 16384 and gs > 64 else None
+        need = lib.load().dclr_fps_workspace_bytes(nb, cls) if cls > 16384 else 0
+        ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=device) if need else None
+        _call('dclr_fps_clouds_grouped_ragged', 'fps_ragged[%dx%d]' % (nb, cls), nb, cls, c, npoint, refs, idx.data_ptr(),
+              gpts.data_ptr(), gbox.data_ptr(), lib.ptr(sbox), lib.ptr(ws), need, lib.stream_ptr())
+        _call('dclr_sa_msg_fused_ragged', 'sa_msg_ragged[%dx%d]' % (nb, cls), f16, nb, cls, c, npoint, refs, idx.data_ptr(), ns,
+              ctypes.cast(radii_h, ctypes.c_void_p), ctypes.cast(nsamp_h, ctypes.c_void_p), ctypes.cast(mlp_h, ctypes.c_void_p),
+              out_rows[k * npoint:e * npoint].data_ptr(), lib.ptr(cnt_all[k:e] if want_counts else None), gpts.data_ptr(),
+              gbox.data_ptr(), lib.ptr(sbox), overflow, lib.stream_ptr())
+        k = e
+    for k in range(n_ragged, b):                                       # outside the classes: one cloud per call
+        x1 = clouds[order[k]].unsqueeze(0)
+        dst = out_rows[k * npoint:(k + 1) * npoint]
+        if single is not None and not want_counts:
+            dst.copy_(single(x1))
+            continue
+        fps, gpts, gbox, sbox = fps_clouds_grouped(x1, npoint)
+        groups = None if gpts is None else (gpts, gbox) + (() if sbox is None else (sbox,))
+        got = sa_msg_fused(x1, fps, radii, nsamples, mlps, want_counts=want_counts, groups=groups, precision=precision,
+                           overflow=overflow)
+        if want_counts:
+            got, cnt = got
+            idx_all[k].copy_(fps[0])
+            cnt_all[k].copy_(cnt[0])
+        dst.copy_(got)
+    if not identity:                                                   # launch order -> input order: one scatter
+        perm = dev[2 * n_ragged:]
+        rows.view(b, npoint, F_STRIDE).index_copy_(0, perm, out_rows.view(b, npoint, F_STRIDE))
+        if want_counts:
+            idx_all = torch.empty_like(idx_all).index_copy_(0, perm, idx_all)
+            cnt_all = torch.empty_like(cnt_all).index_copy_(0, perm, cnt_all)
+    return (rows, idx_all, cnt_all) if want_counts else rows
+
+
 def _xyz_col(stride: int) -> int:
     return {F_STRIDE: 64, E_STRIDE: 256}[stride]
 

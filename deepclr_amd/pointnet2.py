@@ -226,6 +226,33 @@ class PointnetSAModuleMSG(nn.Module):
                 self._range_ok = key
         return rows
 
+    def forward_rows_ragged(self, clouds: List[torch.Tensor]) -> torch.Tensor:
+        """A list of (N_i, 3 + in_feat) clouds of different sizes -> rows F (B*npoint, 68) in list order: one sampler and one
+        set-abstraction launch per size class (ops.cloud_rows_ragged), the same rows as forward_rows on each cloud alone.
+        Clouds outside the classes take forward_rows one by one; the range contract is forward_rows's (the overflow word,
+        and the f32 comparison on the first call after the weights changed)."""
+        ops.check_cloud_list(clouds)
+        if clouds[0].shape[1] != 3 + self._in_feat:
+            raise RuntimeError("expected {} columns per point, got {}".format(3 + self._in_feat, clouds[0].shape[1]))
+        if not self.fused:
+            raise NotImplementedError("sample()/forward_rows() belong to the fused kernel; this module runs composed")
+        mlps = self.packed_mlps()
+        key = self._range_key()                  # decided before forward_rows may pass a check for a cloud of its own
+        check = ops.PRECISION == 'f16x2' and ops.CHECK_RANGE != 'never' and (ops.CHECK_RANGE == 'always' or key != self._range_ok)
+        rows = ops.cloud_rows_ragged(clouds, self.npoint, self.radii, self.nsamples, mlps,
+                                     overflow=self.overflow_ptr if ops.PRECISION == 'f16x2' else None,
+                                     single=self.forward_rows)
+        if check:
+            want = ops.cloud_rows_ragged(clouds, self.npoint, self.radii, self.nsamples, mlps, precision='f32',
+                                         single=self.forward_rows)
+            err, scale = float((rows - want).abs().max()), float(want.abs().max())
+            if not err <= 1e-4 * max(1.0, scale) or not scale < ops.F16_MAX:
+                raise RuntimeError("split-f16 matrix path out of range in set abstraction: features reach {:.4g} "
+                                   "(limit 65504) and differ from the f32 matrix path by {:.3g}; run this checkpoint "
+                                   "with DCLR_PRECISION=f32".format(scale, err))
+            self._range_ok = key
+        return rows
+
     def forward(self, xyz: torch.Tensor, features: Optional[torch.Tensor] = None,
                 new_xyz: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """xyz (B, N, 3), features (B, C, N) or None -> new_xyz (B, npoint, 3), new_features (B, 32*scales, npoint)."""

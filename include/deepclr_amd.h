@@ -301,6 +301,31 @@ int dclr_sa_msg_fused_ov(int f16, int b, int n, int c, int npoint, const float *
  * centroid's ball against the slices of the groups it reaches and loads only those that can hold a neighbour (a quarter of
  * the points on the bench clouds). */
 
+/* ---- clouds of different point counts in one launch ------------------------------------------------------
+ * Real scans differ in size from frame to frame. These two entries take the b clouds of a call as per-cloud records
+ * (device array refs[b], read-only): cloud j is refs[j].n points of c floats at refs[j].pts. One call covers one SIZE
+ * CLASS, named by n_max: (1024, 2048], (2048, 4096], (4096, 8192], (8192, 16384], (16384, 32768] or (32768, 65536]
+ * (DCLR_E_UNSUPPORTED outside 1024 < n_max <= 65536). The class fixes the kernel and its group layout
+ * (dclr_fps_group_layout(n_max)); every buffer is sized by it as for b clouds of n_max points: idx (b, m),
+ * group_pts / group_box / slice_box as dclr_fps_clouds_grouped_batched (slice_box: classes up to 16384 with groups of
+ * more than 64 points, else NULL), workspace as dclr_fps_clouds_grouped_ws for n_max > 16384 (ignored below).
+ * Each workgroup clamps its record's n to [1, class maximum]: a record that lies gives wrong samples, never an access
+ * outside the call's buffers. Records whose n falls in the class give exactly the samples, rows and counts the same
+ * cloud gets alone. Set abstraction takes the sampler's outputs of the same call; group_pts and group_box are required;
+ * overflow as dclr_sa_msg_fused_batched_ov. ABI 0.2, added without a version change. */
+typedef struct DclrCloudRef {
+    const float *pts;                       /* (n, c) f32, row-major */
+    int32_t n;                              /* points */
+    int32_t reserved;                       /* 0 */
+} DclrCloudRef;
+int dclr_fps_clouds_grouped_ragged(int b, int n_max, int c, int m, const DclrCloudRef *refs, int32_t *idx,
+                                   float *group_pts, float *group_box, float *slice_box, void *workspace,
+                                   long long workspace_bytes, dclr_stream_t stream);
+int dclr_sa_msg_fused_ragged(int f16, int b, int n_max, int c, int npoint, const DclrCloudRef *refs, const int32_t *fps_idx,
+                             int n_scales, const float *radii_host, const int *nsamples_host,
+                             const float *const *mlp_host_ptrs, float *out_rows, int32_t *counts, const float *group_pts,
+                             const float *group_box, const float *slice_box, uint32_t *overflow, dclr_stream_t stream);
+
 /* ---- the dense stages of one batch in one call ----------------------------------------------------------
  * Rows F of [templates..., sources...] -> pose outputs y (pairs, n_out): the launches DeepCLR.forward makes
  * after set abstraction (reference: deepclr.py:502-506: merge layers = flow embedding, then the pose head)
