@@ -1,4 +1,5 @@
-"""Build libdeepclr_amd.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libdeepclr_amd.so (inference ABI, include/deepclr_amd.h) and libdeepclr_amd_train.so (training kernels,
+include/deepclr_amd_train.h) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 Every object is compiled with -Rpass-analysis=kernel-resource-usage; the remarks are condensed into
 csrc/<name>.usage.txt (kernel, VGPRs, scratch bytes, occupancy, LDS bytes). kernel_usage() reads them:
@@ -13,6 +14,9 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB = os.path.join(CSRC, 'libdeepclr_amd.so')
 SOURCES = ['api.hip', 'fps.hip', 'grouping.hip', 'knn.hip', 'sa.hip', 'gemm.hip', 'flow.hip', 'gemm16.hip', 'flow16.hip', 'prep.hip', 'forward.hip']
 HEADERS = ['common.h', 'mma.h', 'mma16f.h', os.path.join('..', '..', 'include', 'deepclr_amd.h')]
+TRAIN_LIB = os.path.join(CSRC, 'libdeepclr_amd_train.so')
+TRAIN_SOURCES = ['sa_train.hip']
+TRAIN_HEADERS = HEADERS + [os.path.join('..', '..', 'include', 'deepclr_amd_train.h')]
 # -ffp-contract=off: the distance recipe shared with the oracle is one rounding per operation;
 # MLP code requests FMA explicitly.
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall',
@@ -61,10 +65,9 @@ def _write_usage(path: str, stderr: str) -> str:
     return '\n'.join(l for l in rest if 'kernel-resource-usage' not in l and not l.startswith(' ') or 'error' in l or 'warning' in l)
 
 
-def kernel_usage() -> dict:
-    """{mangled kernel name: {'vgprs', 'agprs', 'scratch', 'occupancy', 'lds'}} from the last build's usage files."""
+def _usage(sources) -> dict:
     out = {}
-    for src in SOURCES:
+    for src in sources:
         path = os.path.join(CSRC, src.replace('.hip', '.usage.txt'))
         if not os.path.exists(path):
             continue
@@ -74,16 +77,31 @@ def kernel_usage() -> dict:
     return out
 
 
+def kernel_usage() -> dict:
+    """{mangled kernel name: {'vgprs', 'agprs', 'scratch', 'occupancy', 'lds'}} from the last build's usage files."""
+    return _usage(SOURCES)
+
+
+def train_kernel_usage() -> dict:
+    """kernel_usage() of libdeepclr_amd_train.so."""
+    return _usage(TRAIN_SOURCES)
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
+    """Both libraries; returns the path of libdeepclr_amd.so."""
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, h) for h in HEADERS]
-    objs, jobs = [], []
-    for src in SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(CSRC, src.replace('.hip', '.o'))
-        objs.append(o)
-        if force or _stale(o, [s] + headers):
-            jobs.append([hipcc, *FLAGS, '-c', s, '-o', o])
+    jobs, links = [], []
+    for lib, sources, header_names in ((LIB, SOURCES, HEADERS), (TRAIN_LIB, TRAIN_SOURCES, TRAIN_HEADERS)):
+        headers = [os.path.join(CSRC, h) for h in header_names]
+        objs, lib_jobs = [], []
+        for src in sources:
+            s = os.path.join(CSRC, src)
+            o = os.path.join(CSRC, src.replace('.hip', '.o'))
+            objs.append(o)
+            if force or _stale(o, [s] + headers):
+                lib_jobs.append([hipcc, *FLAGS, '-c', s, '-o', o])
+        jobs += lib_jobs
+        links.append((lib, objs, bool(lib_jobs)))
 
     def run(cmd):
         if verbose:
@@ -102,8 +120,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
     with ThreadPoolExecutor(max_workers=4) as pool:
         list(pool.map(compile_one, jobs))
-    if force or jobs or _stale(LIB, objs):
-        run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB, *objs])
+    for lib, objs, compiled in links:
+        if force or compiled or _stale(lib, objs):
+            run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib, *objs])
     return LIB
 
 

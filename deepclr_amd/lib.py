@@ -61,6 +61,15 @@ SIGNATURES = {
     'dclr_prepare_cloud': [_i, _i, _p, _i, _i, _f, _f, _i, _p, _p, _p, _p],
 }
 
+# name -> argtypes; every entry point declared in include/deepclr_amd_train.h (libdeepclr_amd_train.so)
+TRAIN_SIGNATURES = {
+    'dclr_train_version': [],
+    'dclr_sa_msg_train_forward': [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    'dclr_sa_msg_train_workspace_bytes': [_i, _i, _i],
+    'dclr_sa_msg_train_backward': [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.c_longlong, _p],
+}
+TRAIN_LIB_PATH = os.path.join(_CSRC, 'libdeepclr_amd_train.so')
+
 MERGE_MAX_LAYERS, MERGE_MAX_FC = 8, 4
 MERGE_EVENTS = 6 + MERGE_MAX_FC
 
@@ -129,6 +138,27 @@ def load() -> ctypes.CDLL:
                           else _i)
         _lib = lib
     return _lib
+
+
+_train_lib: Optional[ctypes.CDLL] = None
+
+
+def load_train() -> ctypes.CDLL:
+    """Load the training library (the fused set abstraction's forward with argmax and its backward); raises if it has not
+    been built."""
+    global _train_lib
+    if _train_lib is None:
+        if not os.path.exists(TRAIN_LIB_PATH):
+            raise RuntimeError(
+                "deepclr_amd: {} is missing. Build it with `python -m deepclr_amd.build` "
+                "(hipcc --offload-arch=gfx950); there is no CPU fallback.".format(TRAIN_LIB_PATH))
+        lib = ctypes.CDLL(TRAIN_LIB_PATH)
+        for name, argtypes in TRAIN_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = ctypes.c_longlong if name == 'dclr_sa_msg_train_workspace_bytes' else _i
+        _train_lib = lib
+    return _train_lib
 
 
 def check(code: int, what: str) -> None:

@@ -118,12 +118,16 @@ class SetAbstraction(DeepCLRModule):
 
     def forward_train(self, clouds: torch.Tensor) -> torch.Tensor:
         """forward() with a gradient: every level composed from the level-1 HIP operators and their HIP backward
-        (gather / group), the shared MLP and the max in torch (PointnetSAModuleMSG._forward_composed, train branch)."""
+        (gather / group), the shared MLP and the max in torch (PointnetSAModuleMSG._forward_composed, train branch) --
+        or, for a level whose fused_training applies (DeepCLR.set_fused_training), the fused training kernels."""
         xyz = clouds[:, :3, :].transpose(1, 2).contiguous()
         feats = clouds[:, 3:, :].contiguous() if clouds.shape[1] > 3 else None
         for level in (self._sa0, self._sa1):
             if level is not None:
-                xyz, feats = level._forward_composed(xyz, feats, train=True)
+                if level.fused_training_applies(xyz, feats):
+                    xyz, feats = level._forward_fused_train(xyz, feats)
+                else:
+                    xyz, feats = level._forward_composed(xyz, feats, train=True)
         return torch.cat((xyz.transpose(1, 2), feats), dim=1).contiguous()
 
     def forward(self, clouds: torch.Tensor, *_args: Any) -> torch.Tensor:
@@ -866,6 +870,25 @@ class DeepCLR(BaseModel):
                 fn = getattr(mod, name, None)
                 if callable(fn) and mod is not self:
                     fn()
+
+    def set_fused_training(self, enabled: bool = True) -> List[str]:
+        """Let a training forward (model.train(), gradients on) run the set-abstraction levels on the fused training
+        kernels (csrc/sa_train.hip) instead of composing them in torch: sets PointnetSAModuleMSG.fused_training on every
+        level. A level takes the fused path only with the fused kernel's shape, no batch norm and an input without
+        gradient -- the first level of the first per-cloud module; a second level or a module behind a `transform`
+        reads features that carry a gradient and stays composed. Returns the names of the levels that will run fused
+        (none with enabled=False)."""
+        fused, grad_in = [], False
+        for i, layer in enumerate(self._cloud_layers):
+            for name in ('_sa0', '_sa1'):
+                level = getattr(layer, name, None)
+                if level is None:
+                    continue
+                level.fused_training = bool(enabled)
+                if enabled and level.fused and not level._bn and not grad_in:
+                    fused.append('_cloud_layers.{}.{}'.format(i, name))
+                grad_in = grad_in or any(p.requires_grad for p in level.parameters())
+        return fused
 
     # -- row-level pipeline (what bench.py and the sharded runner drive) ---------------------------
     def _refuse_off_rows(self, entry: str) -> None:

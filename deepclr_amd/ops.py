@@ -598,3 +598,80 @@ def fc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], act: int)
     _call('dclr_fc', 'fc[%d]' % m, m, n, k, x.data_ptr(), w.data_ptr(), lib.ptr(bias), act, y.data_ptr(),
                                  lib.stream_ptr())
     return y
+
+
+# ------------------------------------------------------------------------------------------------
+# training: the fused set abstraction's forward with argmax and its weight backward (libdeepclr_amd_train.so)
+# ------------------------------------------------------------------------------------------------
+SA_TRAIN_MLP_FLOATS = 896           # per scale: W1 (16 x 4) b1 W2 (16 x 16) b2 W3 (32 x 16) b3 (include/deepclr_amd_train.h)
+
+
+def _call_train(name: str, what: str, *args) -> None:
+    lib.check(getattr(lib.load_train(), name)(*args), what)
+
+
+def pack_sa_train_mlp(params: Sequence[torch.Tensor], in_feat: int) -> torch.Tensor:
+    """Conv weights / biases of the scales, in order [W1 b1 W2 b2 W3 b3] per scale (W (out, in, 1, 1)) -> the flat
+    (scales * 896) buffer of dclr_sa_msg_train_*; W1's feature column is zero when in_feat = 0. Built from the tensors as
+    they are at the call (an optimizer step updates them in place), without gradient (SAMsgTrainFunction has the backward)."""
+    parts = []
+    for j in range(0, len(params), 6):
+        w1, b1, w2, b2, w3, b3 = (t.detach() for t in params[j:j + 6])
+        w1 = w1.reshape(16, 3 + in_feat)
+        if in_feat == 0:
+            w1 = torch.cat((w1, w1.new_zeros(16, 1)), dim=1)
+        parts += [w1.reshape(-1), b1.reshape(-1), w2.reshape(-1), b2.reshape(-1), w3.reshape(-1), b3.reshape(-1)]
+    return torch.cat(parts).to(torch.float32).contiguous()
+
+
+def sa_msg_train_forward(xyz: torch.Tensor, feats: Optional[torch.Tensor], new_xyz: torch.Tensor,
+                         idx: Sequence[torch.Tensor], weights: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """xyz (B, N, 3), feats (B, f, N) (f <= 1) or None, new_xyz (B, npoint, 3), idx: per scale the ball query
+    (B, npoint, nsample) int32, weights (scales * 896) -> features (B, 32 * scales, npoint) and arg (same shape, int32):
+    the point index of the first slot reaching each maximum."""
+    xyz, new_xyz, weights = lib.dev_f32(xyz, 'xyz'), lib.dev_f32(new_xyz, 'new_xyz'), lib.dev_f32(weights, 'weights')
+    b, n, _ = xyz.shape
+    npoint = new_xyz.shape[1]
+    f = 0 if feats is None else lib.dev_f32(feats, 'feats').shape[1]
+    scales = len(idx)
+    for t in idx:
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.shape[:2] == (b, npoint)):
+            raise RuntimeError("idx: (B, npoint, nsample) int32 contiguous GPU tensors from ball_query")
+    if weights.numel() != scales * SA_TRAIN_MLP_FLOATS:
+        raise RuntimeError("weights: {} floats for {} scales".format(scales * SA_TRAIN_MLP_FLOATS, scales))
+    features = torch.empty(b, 32 * scales, npoint, dtype=torch.float32, device=xyz.device)
+    arg = torch.empty(b, 32 * scales, npoint, dtype=torch.int32, device=xyz.device)
+    ns = (ctypes.c_int * scales)(*[t.shape[2] for t in idx])
+    ptrs = (ctypes.c_void_p * scales)(*[t.data_ptr() for t in idx])
+    _call_train('dclr_sa_msg_train_forward', 'sa_msg_train_forward', b, n, f, npoint, scales, ns, xyz.data_ptr(),
+                lib.ptr(feats), new_xyz.data_ptr(), ptrs, weights.data_ptr(), features.data_ptr(), arg.data_ptr(),
+                lib.stream_ptr())
+    return features, arg
+
+
+def sa_msg_train_workspace_bytes(b: int, npoint: int, scales: int) -> int:
+    nbytes = lib.load_train().dclr_sa_msg_train_workspace_bytes(b, npoint, scales)
+    lib.check(nbytes if nbytes < 0 else 0, 'sa_msg_train_workspace_bytes')
+    return nbytes
+
+
+def sa_msg_train_backward(grad_out: torch.Tensor, arg: torch.Tensor, xyz: torch.Tensor, feats: Optional[torch.Tensor],
+                          new_xyz: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """grad_out (B, 32 * scales, npoint) and arg from sa_msg_train_forward on the same inputs -> the gradient of
+    `weights` (scales * 896), bit-identical from run to run."""
+    grad_out = lib.dev_f32(grad_out, 'grad_out')
+    xyz, new_xyz, weights = lib.dev_f32(xyz, 'xyz'), lib.dev_f32(new_xyz, 'new_xyz'), lib.dev_f32(weights, 'weights')
+    b, n, _ = xyz.shape
+    npoint = new_xyz.shape[1]
+    f = 0 if feats is None else lib.dev_f32(feats, 'feats').shape[1]
+    scales = weights.numel() // SA_TRAIN_MLP_FLOATS
+    if not (arg.is_cuda and arg.dtype == torch.int32 and arg.is_contiguous() and arg.shape == grad_out.shape
+            and tuple(grad_out.shape) == (b, 32 * scales, npoint)):
+        raise RuntimeError("grad_out / arg: (B, 32 * scales, npoint), arg int32 from sa_msg_train_forward")
+    nbytes = sa_msg_train_workspace_bytes(b, npoint, scales)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=xyz.device)
+    grad = torch.empty(scales * SA_TRAIN_MLP_FLOATS, dtype=torch.float32, device=xyz.device)
+    _call_train('dclr_sa_msg_train_backward', 'sa_msg_train_backward', b, n, f, npoint, scales, xyz.data_ptr(),
+                lib.ptr(feats), new_xyz.data_ptr(), weights.data_ptr(), grad_out.data_ptr(), arg.data_ptr(),
+                grad.data_ptr(), ws.data_ptr(), nbytes, lib.stream_ptr())
+    return grad

@@ -16,6 +16,10 @@ reference itself composes (furthest_point_sample, gather_operation, ball_query, 
 f32-MFMA ``dclr_linear`` for the shared MLP with the max over nsample folded into its last layer; torch only
 concatenates, pads and reshapes in between. That path is unfused and materialises the grouped tensor, as the
 reference does; it exists for coverage, not for speed.
+
+Training: with ``fused_training`` set (DeepCLR.set_fused_training), a forward with a gradient of the fused shape, without
+batch norm and on inputs that carry no gradient runs SAMsgTrainFunction (csrc/sa_train.hip): the pooled features and each
+channel's argmax point, and a backward for the shared MLP's weights only.
 """
 from typing import List, Optional, Tuple
 
@@ -66,6 +70,39 @@ class GroupingOperation(torch.autograd.Function):
 
 gather_operation = GatherOperation.apply
 grouping_operation = GroupingOperation.apply
+
+
+class SAMsgTrainFunction(torch.autograd.Function):
+    """The fused set abstraction with a backward for its shared-MLP weights (csrc/sa_train.hip): inputs xyz (B, N, 3),
+    features (B, f, N) or None, centroids (B, npoint, 3), radii, nsamples, then per scale the conv weights and biases
+    W1 b1 W2 b2 W3 b3 -> features (B, 32 * scales, npoint). The ball-query indices live only inside forward; backward
+    recomputes each pooled channel's argmax neighbour. The network input carries no gradient here (callers check)."""
+
+    @staticmethod
+    def forward(ctx, xyz, features, new_xyz, radii, nsamples, *params):
+        in_feat = 0 if features is None else features.shape[1]
+        weights = ops.pack_sa_train_mlp(params, in_feat)          # per call: optimizer steps update params in place
+        idx = [ops.ball_query(r, s, xyz, new_xyz) for r, s in zip(radii, nsamples)]
+        out, arg = ops.sa_msg_train_forward(xyz, features, new_xyz, idx, weights)
+        ctx.save_for_backward(xyz, features, new_xyz, weights, arg)
+        ctx.shapes = [p.shape for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        xyz, features, new_xyz, weights, arg = ctx.saved_tensors
+        grad = ops.sa_msg_train_backward(grad_out.contiguous(), arg, xyz, features, new_xyz, weights)
+        grads = []
+        for j, shape in enumerate(ctx.shapes):
+            base = (j // 6) * ops.SA_TRAIN_MLP_FLOATS
+            k = j % 6
+            if k == 0:                                             # W1 (16, c_in, 1, 1): columns of the (16, 4) block
+                grads.append(grad.as_strided(tuple(shape), (4, 1, 1, 1), base))
+            else:
+                offset = base + (64, 80, 336, 352, 864)[k - 1]
+                grads.append(grad.narrow(0, offset, shape.numel()).view(shape))
+        return (None, None, None, None, None, *grads)
+
 
 _FUSED_MLP = [16, 16, 32]
 
@@ -140,6 +177,9 @@ class PointnetSAModuleMSG(nn.Module):
         self.differentiable = False              # True: forward() takes the composed, differentiable path whenever a
                                                  # gradient is wanted, also for shapes the fused kernel covers
         self.fused = fused                       # one-kernel path (csrc/sa.hip); otherwise level-1 operators + dclr_linear
+        self.fused_training = False              # True: a forward with a gradient takes the fused training kernels
+                                                 # (csrc/sa_train.hip) where fused_training_applies(); set_fused_training
+        self._bn = bool(bn)
         self._cache = PackedCache()
         self._cache_composed = PackedCache()
         self._range_ok = None                    # weights key of the last checked split-f16 pass (ops.CHECK_RANGE)
@@ -253,6 +293,23 @@ class PointnetSAModuleMSG(nn.Module):
             self._range_ok = key
         return rows
 
+    def fused_training_applies(self, xyz: torch.Tensor, features: Optional[torch.Tensor]) -> bool:
+        """A forward with a gradient on these inputs takes _forward_fused_train: the flag is set, the shape is the fused
+        kernel's, no batch norm, and the input carries no gradient (the kernels differentiate the weights only)."""
+        return (self.fused_training and self.fused and not self._bn and not xyz.requires_grad
+                and not (features is not None and features.requires_grad))
+
+    def _forward_fused_train(self, xyz: torch.Tensor, features: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """_forward_composed(train=True) on the fused training kernels: the same centroids, neighbour sets and features,
+        the weights' gradient from the argmax neighbours alone (O(centroids) memory instead of every activation)."""
+        xyz = xyz.detach().contiguous()
+        feats = None if features is None else features.detach().contiguous()
+        idx = ops.furthest_point_sample(xyz, self.npoint)
+        new_xyz = ops.gather_operation(xyz.transpose(1, 2).contiguous(), idx).transpose(1, 2).contiguous()
+        params = [p for stack in self.mlps for u in stack for p in (u.conv.weight, u.conv.bias)]
+        out = SAMsgTrainFunction.apply(xyz, feats, new_xyz, self.radii, self.nsamples, *params)
+        return new_xyz, out
+
     def forward(self, xyz: torch.Tensor, features: Optional[torch.Tensor] = None,
                 new_xyz: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """xyz (B, N, 3), features (B, C, N) or None -> new_xyz (B, npoint, 3), new_features (B, 32*scales, npoint)."""
@@ -261,9 +318,11 @@ class PointnetSAModuleMSG(nn.Module):
         if (0 if features is None else features.shape[1]) != self._in_feat:
             raise RuntimeError("expected {} feature channels, got {}".format(
                 self._in_feat, 0 if features is None else features.shape[1]))
-        if not self.fused or (torch.is_grad_enabled() and (xyz.requires_grad or (features is not None and features.requires_grad)
-                                                           or any(p.requires_grad for p in flat_parameters(self)))
-                              and self.differentiable):
+        grad = torch.is_grad_enabled() and (xyz.requires_grad or (features is not None and features.requires_grad)
+                                            or any(p.requires_grad for p in flat_parameters(self)))
+        if grad and self.differentiable and self.fused_training_applies(xyz, features):
+            return self._forward_fused_train(xyz, features)
+        if not self.fused or (grad and self.differentiable):
             return self._forward_composed(xyz, features)
         clouds = xyz if features is None else torch.cat((xyz, features.transpose(1, 2)), dim=2)
         rows = self.forward_rows(clouds.contiguous())

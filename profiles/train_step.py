@@ -1,0 +1,80 @@
+"""One training step (forward + loss + backward + SGD step) with the set abstraction composed in torch and with the fused
+training kernels (DeepCLR.set_fused_training): median ms per step and torch.cuda.max_memory_allocated.
+
+    python profiles/train_step.py --workload kitti16k [--steps 10 --warmup 3] [--json out.json]
+
+Workloads: kitti16k (5 pairs of 2 x 16384 x 4), kitti64k (5 pairs of 2 x 65536 x 4), modelnet (5 pairs of 2 x 1024 x 3),
+all with the shipped model shapes. One workload per process, so that each can run under its own time limit."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from deepclr_amd import synthetic  # noqa: E402
+from deepclr_amd.config import model_config_from_dict  # noqa: E402
+from deepclr_amd.labels import LabelType  # noqa: E402
+from deepclr_amd.models import build_model  # noqa: E402
+
+WORKLOADS = {'kitti16k': ('kitti', 16384), 'kitti64k': ('kitti', 65536), 'modelnet': ('modelnet', 1024)}
+PAIRS = 5
+
+
+def run(workload: str, fused: bool, steps: int, warmup: int) -> dict:
+    kind, n = WORKLOADS[workload]
+    cfg = synthetic.model_cfg(kind)
+    cfg['params']['loss'] = {'name': 'TransformLoss', 'params': {'p': 2, 'sx': 1.0, 'sq': 10.0}}
+    model = build_model(model_config_from_dict(cfg))
+    model.load_state_dict(synthetic.random_state_dict(cfg, seed=0), strict=False)
+    model = model.to('cuda:0').train()
+    levels = model.set_fused_training(fused)
+    x = torch.from_numpy(synthetic.make_batch(kind, PAIRS, n)).to('cuda:0')
+    y = torch.from_numpy(np.stack([LabelType.POSE3D_DUAL_QUAT.from_matrix(synthetic.kitti_like_pair(i, 16)[2])
+                                   for i in range(PAIRS)]).astype(np.float32)).to('cuda:0')
+    m = torch.eye(4, device='cuda:0').expand(2 * PAIRS, 4, 4).contiguous()
+    opt = torch.optim.SGD([p for name, p in model.named_parameters() if not name.startswith('_loss_layer')], lr=1e-6)
+    times = []
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    for i in range(warmup + steps):
+        t0 = time.perf_counter()
+        opt.zero_grad(set_to_none=True)
+        _, loss, _ = model(x.clone(), m=m, y=y)
+        loss.backward()
+        opt.step()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            times.append(1e3 * (time.perf_counter() - t0))
+    return {'workload': workload, 'sa': 'fused' if fused else 'composed', 'fused_levels': levels,
+            'median_ms': statistics.median(times), 'min_ms': min(times), 'steps': steps,
+            'max_memory_allocated_mb': torch.cuda.max_memory_allocated() / 2 ** 20, 'loss': float(loss.detach())}
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument('--workload', choices=sorted(WORKLOADS), required=True)
+    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--json', default=None, help='append the two result lines to this file')
+    args = ap.parse_args()
+    rows = []
+    for fused in (False, True):
+        torch.cuda.empty_cache()
+        rows.append(run(args.workload, fused, args.steps, args.warmup))
+        print('%-9s %-8s median %9.2f ms/step  peak %9.1f MB  loss %.6f' % (
+            rows[-1]['workload'], rows[-1]['sa'], rows[-1]['median_ms'], rows[-1]['max_memory_allocated_mb'], rows[-1]['loss']),
+            flush=True)
+    if args.json:
+        with open(args.json, 'a') as f:
+            for r in rows:
+                f.write(json.dumps(r) + '\n')
+
+
+if __name__ == '__main__':
+    main()
