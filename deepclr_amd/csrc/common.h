@@ -31,6 +31,16 @@ DCLR_INTERNAL int dclr_x_flow_embedding_fused_f16(int pairs, int npoint, int k, 
                                                   const void *w3p, const float *b3, float *e_rows, float *zero,
                                                   long long zero_count, uint32_t *overflow, dclr_stream_t stream);
 
+// What dclr_head_conv_fused / dclr_x_head_conv_fused_f16 / dclr_x_fc would refuse, without launching anything (the one-call
+// entry points check every stage before their first launch)
+DCLR_INTERNAL int dclr_x_head_conv_fused_check(int m, int n_layers, const int *k_host, const int *n_host,
+                                               const float *const *w_packed_host, const float *const *bias_host,
+                                               const float *x, int ldx, const float *colmax, int rows_per_group);
+DCLR_INTERNAL int dclr_x_head_conv_fused_f16_check(int m, int n_layers, int k_in, const int *k_host, const int *n_host,
+                                                   const void *const *w_packed_host, const float *const *bias_host,
+                                                   const float *x, int ldx, const float *colmax, int rows_per_group);
+DCLR_INTERNAL int dclr_x_fc_check(int m, int n, int k, const float *x, const float *w, int act, const float *y);
+
 // dclr_fc with the overflow word as `poison`: set -> the outputs are written as NaN (the last layer of dclr_merge_forward)
 DCLR_INTERNAL int dclr_x_fc(int m, int n, int k, const float *x, const float *w, const float *bias, int act, float *y,
                             const uint32_t *poison, dclr_stream_t stream);

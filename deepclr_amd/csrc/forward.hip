@@ -12,14 +12,37 @@ extern "C" int dclr_merge_forward(const DclrMergeArgs *a, void *const *events, d
                  a->stages >= 1 && a->stages <= 3);
     DCLR_REQUIRE(a->f_rows && a->pt && a->ps && a->knn_idx);
     DCLR_REQUIRE(!(a->stages & 2) || (a->e_rows && a->colmax && a->y && a->fc_tmp[0] && a->fc_tmp[1]));
+    const int rows = a->pairs * a->npoint;
+    int rc;
+    // Everything the calls below would refuse, refused before the first launch (DCLR_E_* = nothing enqueued): the kNN
+    // rank selection and the flow kernels' k, the head's widths, every fc layer (its input width the previous output width).
+    if (a->stages & 1) DCLR_REQUIRE(a->k >= 1 && a->npoint >= a->k && a->pairs <= 65535);
+    if (a->stages & 2) {
+        if (a->k < 1 || a->k > 32) return DCLR_E_UNSUPPORTED;
+        DCLR_REQUIRE(a->w1a && a->b1 && a->w2 && a->b2 && a->w3 && a->b3);
+        DCLR_REQUIRE(((uintptr_t)a->w2 & 15) == 0 && ((uintptr_t)a->w3 & 15) == 0 && ((uintptr_t)a->pt & 7) == 0 &&
+                     ((uintptr_t)a->ps & 7) == 0 && (a->precision == 0 || ((uintptr_t)a->b2 & 15) == 0));
+        rc = a->precision == 1
+                 ? dclr_x_head_conv_fused_f16_check(rows, a->n_head_layers, a->head_k_in, a->head_k, a->head_n, a->head_w,
+                                                    a->head_b, a->e_rows, DCLR_E_STRIDE, a->colmax, a->npoint)
+                 : dclr_x_head_conv_fused_check(rows, a->n_head_layers, a->head_k, a->head_n,
+                                                (const float *const *)a->head_w, a->head_b, a->e_rows, DCLR_E_STRIDE,
+                                                a->colmax, a->npoint);
+        if (rc != DCLR_OK) return rc;
+        int k_prev = a->head_n[a->n_head_layers - 1];
+        for (int l = 0; l < a->n_fc; ++l) {
+            DCLR_REQUIRE(a->fc_k[l] == k_prev);
+            rc = dclr_x_fc_check(a->pairs, a->fc_n[l], a->fc_k[l], a->colmax, a->fc_w[l], a->fc_act[l], a->y);
+            if (rc != DCLR_OK) return rc;
+            k_prev = a->fc_n[l];
+        }
+    }
     hipStream_t st = (hipStream_t)stream;
     int slot = 0;
     auto mark = [&]() {
         if (events && events[slot]) (void)hipEventRecord((hipEvent_t)events[slot], st);
         ++slot;
     };
-    const int rows = a->pairs * a->npoint;
-    int rc;
     mark();
     if (a->stages & 1) {
         // per-point halves of flow layer 1: W1b * feat_t (templates), W1c * feat_s (sources), one launch

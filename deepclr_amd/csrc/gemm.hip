@@ -236,7 +236,9 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_fused_kernel(HeadParams 
 // One wave per output column, 4 columns per workgroup. The <= FC_ROWS input rows are staged in LDS
 // once per workgroup; a wave keeps the whole weight row in flight (K/64 coalesced loads issued back
 // to back -- a serial load-use loop costs one L2 round trip per 64 weights) and reduces the per-lane
-// partial sums with DPP adds.
+// partial sums with DPP adds. A row longer than FC_MAX_K runs in chunks of FC_MAX_K: stage, then
+// accumulate on into the same per-lane sums (one lane's fmaf order is that of one long chunk), and the
+// weights are loaded again per chunk. k <= FC_MAX_K is one chunk, its weights loaded once per launch.
 constexpr int FC_WAVES = 4, FC_ROWS = 8, FC_MAX_K = 1024, FC_CHUNKS = FC_MAX_K / 64;
 
 __device__ __forceinline__ float fc_wave_sum(float v) {
@@ -258,9 +260,10 @@ __global__ __launch_bounds__(FC_WAVES * 64) void fc_kernel(int m, int n, int k, 
     const bool bad = poison != nullptr && __hip_atomic_load(poison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u;
     const int col = blockIdx.x * FC_WAVES + wave;
     const bool live = col < n;                                       // wave-uniform
+    const bool one_chunk = k <= FC_MAX_K;                            // uniform
+    const float *wr = w + (size_t)col * k;
     float wv[FC_CHUNKS];
-    if (live) {
-        const float *wr = w + (size_t)col * k;
+    if (live && one_chunk) {
 #pragma unroll
         for (int c = 0; c < FC_CHUNKS; ++c) wv[c] = c * 64 + lane < k ? wr[c * 64 + lane] : 0.f;
     }
@@ -269,29 +272,38 @@ __global__ __launch_bounds__(FC_WAVES * 64) void fc_kernel(int m, int n, int k, 
     // instead of queueing inside one workgroup per column group
     for (int r0 = blockIdx.y * FC_ROWS; r0 < m; r0 += gridDim.y * FC_ROWS) {
         const int rows = m - r0 < FC_ROWS ? m - r0 : FC_ROWS;
-        __syncthreads();
-        if ((k & 3) == 0 && ((uintptr_t)x & 15) == 0) {              // 16 bytes per lane and request (a quarter of the instructions)
-            for (int r = 0; r < FC_ROWS; ++r)
-                for (int kk = 4 * tid; kk < k; kk += FC_WAVES * 64 * 4)
-                    *reinterpret_cast<float4 *>(&xs[r][kk]) =
-                        r < rows ? *reinterpret_cast<const float4 *>(x + (size_t)(r0 + r) * k + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
-            for (int r = 0; r < FC_ROWS; ++r)
-                for (int kk = tid; kk < k; kk += FC_WAVES * 64)
-                    xs[r][kk] = r < rows ? x[(size_t)(r0 + r) * k + kk] : 0.f;
-        }
-        __syncthreads();
-        if (!live) continue;
         float acc[FC_ROWS];
 #pragma unroll
         for (int r = 0; r < FC_ROWS; ++r) acc[r] = 0.f;
+        for (int k0 = 0; k0 < k; k0 += FC_MAX_K) {
+            const int kc = k - k0 < FC_MAX_K ? k - k0 : FC_MAX_K;  // columns of this chunk
+            if (live && !one_chunk) {
 #pragma unroll
-        for (int c = 0; c < FC_CHUNKS; ++c) {
-            if (c * 64 < k) {                                        // uniform
+                for (int c = 0; c < FC_CHUNKS; ++c) wv[c] = c * 64 + lane < kc ? wr[k0 + c * 64 + lane] : 0.f;
+            }
+            __syncthreads();
+            if ((k & 3) == 0 && ((uintptr_t)x & 15) == 0) {          // 16 bytes per lane and request (a quarter of the instructions)
+                for (int r = 0; r < FC_ROWS; ++r)
+                    for (int kk = 4 * tid; kk < kc; kk += FC_WAVES * 64 * 4)
+                        *reinterpret_cast<float4 *>(&xs[r][kk]) =
+                            r < rows ? *reinterpret_cast<const float4 *>(x + (size_t)(r0 + r) * k + k0 + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                for (int r = 0; r < FC_ROWS; ++r)
+                    for (int kk = tid; kk < kc; kk += FC_WAVES * 64)
+                        xs[r][kk] = r < rows ? x[(size_t)(r0 + r) * k + k0 + kk] : 0.f;
+            }
+            __syncthreads();
+            if (live) {
 #pragma unroll
-                for (int r = 0; r < FC_ROWS; ++r) acc[r] = fmaf(wv[c], xs[r][c * 64 + lane < k ? c * 64 + lane : 0], acc[r]);
+                for (int c = 0; c < FC_CHUNKS; ++c) {
+                    if (c * 64 < kc) {                               // uniform
+#pragma unroll
+                        for (int r = 0; r < FC_ROWS; ++r) acc[r] = fmaf(wv[c], xs[r][c * 64 + lane < kc ? c * 64 + lane : 0], acc[r]);
+                    }
+                }
             }
         }
+        if (!live) continue;
         // The eight rows' wave sums in ten exchanges instead of 48: the butterfly (xor 32, 16, ..., 1) of fc_wave_sum, but a
         // lane keeps only half of its rows at each of the first three steps and hands the other half to its partner --
         // the same pairs are added at every level (a + b == b + a bit for bit), so every row's sum is the one
@@ -386,20 +398,31 @@ extern "C" int dclr_linear_pair(int m_each, int n, int kp, const float *x, int l
     return dclr_launch_status();
 }
 
-extern "C" int dclr_head_conv_fused(int m, int n_layers, const int *k_host, const int *n_host,
-                                    const float *const *w_packed_host, const float *const *bias_host, const float *x,
-                                    int ldx, float *colmax, int rows_per_group, dclr_stream_t stream) {
+int dclr_x_head_conv_fused_check(int m, int n_layers, const int *k_host, const int *n_host,
+                                 const float *const *w_packed_host, const float *const *bias_host, const float *x, int ldx,
+                                 const float *colmax, int rows_per_group) {
     DCLR_REQUIRE(m > 0 && n_layers >= 1 && k_host && n_host && w_packed_host && bias_host && x && colmax);
     DCLR_REQUIRE(m % HEAD_ROWS == 0 && rows_per_group > 0 && rows_per_group % HEAD_ROWS == 0 && m % rows_per_group == 0);
     DCLR_REQUIRE(ldx % 4 == 0 && ldx >= k_host[0] && ((uintptr_t)x & 15) == 0);
     if (n_layers > HEAD_MAX_LAYERS) return DCLR_E_UNSUPPORTED;
-    HeadParams prm{};
-    prm.n_layers = n_layers;
     for (int l = 0; l < n_layers; ++l) {
         DCLR_REQUIRE(w_packed_host[l] && bias_host[l] && k_host[l] > 0 && n_host[l] > 0);
         DCLR_REQUIRE(k_host[l] % 8 == 0 && n_host[l] % 32 == 0 && ((uintptr_t)w_packed_host[l] & 15) == 0);
         if (l > 0) DCLR_REQUIRE(k_host[l] == n_host[l - 1]);
         if (k_host[l] > HEAD_MAX_WIDTH || (l + 1 < n_layers && n_host[l] > HEAD_MAX_WIDTH)) return DCLR_E_UNSUPPORTED;
+    }
+    return DCLR_OK;
+}
+
+extern "C" int dclr_head_conv_fused(int m, int n_layers, const int *k_host, const int *n_host,
+                                    const float *const *w_packed_host, const float *const *bias_host, const float *x,
+                                    int ldx, float *colmax, int rows_per_group, dclr_stream_t stream) {
+    const int rc = dclr_x_head_conv_fused_check(m, n_layers, k_host, n_host, w_packed_host, bias_host, x, ldx, colmax,
+                                                rows_per_group);
+    if (rc != DCLR_OK) return rc;
+    HeadParams prm{};
+    prm.n_layers = n_layers;
+    for (int l = 0; l < n_layers; ++l) {
         prm.k[l] = k_host[l];
         prm.n[l] = n_host[l];
         prm.w[l] = reinterpret_cast<const float4 *>(w_packed_host[l]);
@@ -415,10 +438,15 @@ extern "C" int dclr_fc(int m, int n, int k, const float *x, const float *w, cons
     return dclr_x_fc(m, n, k, x, w, bias, act, y, nullptr, stream);
 }
 
+int dclr_x_fc_check(int m, int n, int k, const float *x, const float *w, int act, const float *y) {
+    DCLR_REQUIRE(m > 0 && n > 0 && k > 0 && x && w && y && act >= 0 && act <= 3);
+    return DCLR_OK;
+}
+
 int dclr_x_fc(int m, int n, int k, const float *x, const float *w, const float *bias, int act, float *y,
               const uint32_t *poison, dclr_stream_t stream) {
-    DCLR_REQUIRE(m > 0 && n > 0 && k > 0 && x && w && y && act >= 0 && act <= 3);
-    if (k > FC_MAX_K) return DCLR_E_UNSUPPORTED;
+    const int rc = dclr_x_fc_check(m, n, k, x, w, act, y);
+    if (rc != DCLR_OK) return rc;
     const int row_blocks = (m + FC_ROWS - 1) / FC_ROWS;
     hipLaunchKernelGGL(fc_kernel, dim3((n + FC_WAVES - 1) / FC_WAVES, row_blocks < 64 ? row_blocks : 64), dim3(FC_WAVES * 64), 0,
                        (hipStream_t)stream, m, n, k, x, w, bias, act, y, poison);

@@ -288,23 +288,34 @@ extern "C" int dclr_head_conv_fused_f16(int m, int n_layers, int k_in, const int
                                       rows_per_group, nullptr, stream);
 }
 
-int dclr_x_head_conv_fused_f16(int m, int n_layers, int k_in, const int *k_host, const int *n_host,
-                               const void *const *w_packed_host, const float *const *bias_host, const float *x, int ldx,
-                               float *colmax, int rows_per_group, uint32_t *overflow, dclr_stream_t stream) {
+int dclr_x_head_conv_fused_f16_check(int m, int n_layers, int k_in, const int *k_host, const int *n_host,
+                                     const void *const *w_packed_host, const float *const *bias_host, const float *x,
+                                     int ldx, const float *colmax, int rows_per_group) {
     DCLR_REQUIRE(m > 0 && n_layers >= 1 && k_host && n_host && w_packed_host && bias_host && x && colmax);
     DCLR_REQUIRE(m % 32 == 0 && rows_per_group > 0 && rows_per_group % 32 == 0 && m % rows_per_group == 0);
     DCLR_REQUIRE(k_in > 0 && k_in % 8 == 0 && ldx % 4 == 0 && ldx >= k_in && k_in <= k_host[0] && ((uintptr_t)x & 15) == 0);
     if (n_layers > H16_MAX_LAYERS) return DCLR_E_UNSUPPORTED;
-    Head16Params prm{};
-    prm.n_layers = n_layers;
-    prm.k_in = k_in;
-    prm.overflow = overflow;
     for (int l = 0; l < n_layers; ++l) {
         DCLR_REQUIRE(w_packed_host[l] && bias_host[l] && k_host[l] > 0 && n_host[l] > 0);
         DCLR_REQUIRE(k_host[l] % 16 == 0 && n_host[l] % 32 == 0 && ((uintptr_t)w_packed_host[l] & 15) == 0 &&
                      ((uintptr_t)bias_host[l] & 15) == 0);
         if (l > 0) DCLR_REQUIRE(k_host[l] == n_host[l - 1]);
         if (k_host[l] > H16_MAX_WIDTH || (l + 1 < n_layers && n_host[l] > H16_MAX_WIDTH)) return DCLR_E_UNSUPPORTED;
+    }
+    return DCLR_OK;
+}
+
+int dclr_x_head_conv_fused_f16(int m, int n_layers, int k_in, const int *k_host, const int *n_host,
+                               const void *const *w_packed_host, const float *const *bias_host, const float *x, int ldx,
+                               float *colmax, int rows_per_group, uint32_t *overflow, dclr_stream_t stream) {
+    const int rc = dclr_x_head_conv_fused_f16_check(m, n_layers, k_in, k_host, n_host, w_packed_host, bias_host, x, ldx,
+                                                    colmax, rows_per_group);
+    if (rc != DCLR_OK) return rc;
+    Head16Params prm{};
+    prm.n_layers = n_layers;
+    prm.k_in = k_in;
+    prm.overflow = overflow;
+    for (int l = 0; l < n_layers; ++l) {
         prm.k[l] = k_host[l];
         prm.n[l] = n_host[l];
         prm.w[l] = reinterpret_cast<const float4 *>(w_packed_host[l]);

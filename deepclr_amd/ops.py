@@ -591,9 +591,15 @@ def flow_embedding_fused(f_rows: torch.Tensor, knn_idx: torch.Tensor, pt: torch.
 
 
 def fc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], act: int) -> torch.Tensor:
+    """act(x @ w.T + bias): x (m, k), w (n, k), bias (n,) or None; act 0 none, 1 relu, 2 dual quaternion (sigmoid on
+    column 0, tanh on 1..3), 3 quaternion (sigmoid on column 3, tanh on 4..)."""
     x, w = lib.dev_f32(x, 'x'), lib.dev_f32(w, 'w')
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1]:
+        raise RuntimeError("fc: x (m, k) and w (n, k) expected, got {} and {}".format(tuple(x.shape), tuple(w.shape)))
     m, k = x.shape
     n = w.shape[0]
+    if bias is not None and tuple(lib.dev_f32(bias, 'bias').shape) != (n,):
+        raise RuntimeError("fc: bias of shape ({},) expected, got {}".format(n, tuple(bias.shape)))
     y = torch.empty(m, n, dtype=torch.float32, device=x.device)
     _call('dclr_fc', 'fc[%d]' % m, m, n, k, x.data_ptr(), w.data_ptr(), lib.ptr(bias), act, y.data_ptr(),
                                  lib.stream_ptr())

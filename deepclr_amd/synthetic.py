@@ -24,6 +24,8 @@ from typing import Dict, Tuple
 import numpy as np
 import torch
 
+from .labels import LabelType
+
 
 def _arch(input_dim, npoint, radii, nsamples, k, radius):
     return {
@@ -195,8 +197,9 @@ def state_dict_shapes(cfg: dict) -> 'OrderedDict[str, Tuple[int, ...]]':
     stack('_merge_layers.1.conv', [3 + me['mlp'][-1], *out['mlp']], True)
     lin = out['linear']
     stack('_merge_layers.1.linear', lin, False, step=2 if float(prm.get('dropout', 1.0)) < 1.0 else 1)
-    shapes['_merge_layers.1.output.weight'] = (8, lin[-1])
-    shapes['_merge_layers.1.output.bias'] = (8,)
+    dim = LabelType.create(cfg['label_type']).dim   # 6 / 7 / 8 outputs (reference deepclr.py:275)
+    shapes['_merge_layers.1.output.weight'] = (dim, lin[-1])
+    shapes['_merge_layers.1.output.bias'] = (dim,)
     return shapes
 
 
@@ -204,9 +207,12 @@ def random_state_dict(cfg: dict, seed: int = 0, bias_scale: float = 0.05) -> Dic
     """Xavier-uniform-scaled weights and small non-zero biases from numpy's PCG64.
 
     Non-zero biases (unlike the reference's zero init, helper.py:23-25) so that
-    every bias path of the kernels is exercised by the parity tests.
+    every bias path of the kernels is exercised by the parity tests. The output
+    layer has `label_type.dim` rows; its bias lies around `LabelType.bias` where
+    the label type has one.
     """
     rng = np.random.default_rng(seed)
+    label_bias = LabelType.create(cfg['label_type']).bias
     sd: Dict[str, torch.Tensor] = OrderedDict()
     for name, shape in state_dict_shapes(cfg).items():
         if name.endswith('.num_batches_tracked'):
@@ -223,7 +229,7 @@ def random_state_dict(cfg: dict, seed: int = 0, bias_scale: float = 0.05) -> Dic
             arr = rng.uniform(-bound, bound, size=shape)
         else:
             arr = rng.uniform(-bias_scale, bias_scale, size=shape)
-            if name == '_merge_layers.1.output.bias':
-                arr[0] += 1.0
+            if name == '_merge_layers.1.output.bias' and label_bias is not None:
+                arr += np.array(label_bias)         # around the reference's bias init (deepclr.py:278-281)
         sd[name] = torch.from_numpy(arr.astype(np.float32))
     return sd

@@ -229,7 +229,8 @@ int dclr_flow_embedding_fused(int pairs, int npoint, int k, float radius, const 
 
 /* Fully connected tail on a handful of rows: y (m,n) = act(x (m,k) * w (n,k)^T + bias).
  * act: 0 none, 1 relu, 2 dual-quaternion head (sigmoid on column 0, tanh on 1..3; reference
- * OutputSimple._output_activation, deepclr.py:279-281), 3 quaternion head (sigmoid col 3, tanh 4..6). */
+ * OutputSimple._output_activation, deepclr.py:279-281), 3 quaternion head (sigmoid col 3, tanh 4..6).
+ * Any k > 0: rows wider than 1024 columns run in chunks of 1024 (the sums of k <= 1024 do not change). */
 int dclr_fc(int m, int n, int k, const float *x, const float *w, const float *bias, int act, float *y,
             dclr_stream_t stream);
 
@@ -371,6 +372,8 @@ typedef struct DclrMergeArgs {
                                              * While it is set the last fully connected layer writes y as NaN (ABI 0.2): a
                                              * clamped forward never hands out plausible-looking poses */
 } DclrMergeArgs;
+/* Every size, width and activation the stages would refuse is checked before the first launch (fc_k[0] must be
+ * head_n[last], fc_k[l] fc_n[l - 1]): a DCLR_E_* return has enqueued nothing. */
 int dclr_merge_forward(const DclrMergeArgs *args, void *const *events, dclr_stream_t stream);
 
 /* ---- the per-cloud stages of one launch group in one call ------------------------------------------------

@@ -36,6 +36,15 @@ import oracle                                    # noqa: E402
 import helpers                                   # noqa: E402  (tests/helpers.py: configurations shared with the tests)
 from oracle import labels as olabels             # noqa: E402
 from deepclr_amd import synthetic                # noqa: E402
+from deepclr_amd.labels import LabelType         # noqa: E402
+
+
+def _compose_rigid(t, r, z):
+    """transforms3d.affines.compose(T, R, Z) for Z = ones(3) (no scale, no shear), the only form labels.py calls."""
+    assert np.array_equal(np.asarray(z), np.ones(3))
+    m = np.eye(4)
+    m[:3, :3], m[:3, 3] = r, t
+    return m
 
 
 def _load_reference(ref_root: str):
@@ -64,8 +73,11 @@ def _load_reference(ref_root: str):
     t3d.quaternions.quat2mat = olabels.quat2mat
     t3d.quaternions.qmult = olabels.qmult
     t3d.quaternions.qconjugate = olabels.qconjugate
+    t3d.affines = types.ModuleType('transforms3d.affines')       # compose(T, R, ones(3)): the rigid 4x4 of POSE3D_QUAT
+    t3d.affines.compose = _compose_rigid
     sys.modules['transforms3d'] = t3d
     sys.modules['transforms3d.quaternions'] = t3d.quaternions
+    sys.modules['transforms3d.affines'] = t3d.affines
 
     ign = pkg('ignite')
     ign_utils = types.ModuleType('ignite._utils')
@@ -131,6 +143,28 @@ def loss_golden(ref, out_dir: str) -> None:
     print('wrote losses.npz')
 
 
+def label_loss_golden(ref, out_dir: str) -> None:
+    """losses.npz for the other two label types: quaternion labels (normalised rotation part) and euler labels (no
+    normalisation; angles in degrees, hence the wider spread of columns 3..5)."""
+    LabelType = sys.modules['deepclr.data.labels'].LabelType
+    rng = np.random.default_rng(6)
+    out = {}
+    for name, scale in (('POSE3D_QUAT', np.ones(7)), ('POSE3D_EULER', np.array([1.0, 1.0, 1.0, 30.0, 30.0, 30.0]))):
+        lt = LabelType.create(name)
+        y_pred = torch.from_numpy((rng.normal(size=(8, lt.dim)) * scale).astype(np.float32))
+        y = torch.from_numpy((rng.normal(size=(8, lt.dim)) * scale).astype(np.float32))
+        out[name + '_y_pred'], out[name + '_y'] = y_pred.numpy(), y.numpy()
+        for p in (1, 2):
+            fixed = ref.TransformLoss(lt, p=p, sx=1.5, sq=40.0)
+            learned = ref.TransformUncertaintyLoss(lt, p=p, sx=0.3, sq=-2.5)
+            both = ref.AccumulatedLoss([fixed, ref.TransformLoss(lt, p=p, sx=0.5, sq=2.0)])
+            t, r = ref.TransformLossCalculation(lt, p)(y_pred, y)
+            out['%s_p%d' % (name, p)] = np.array([t.item(), r.item(), fixed(y_pred, y).item(), learned(y_pred, y).item(),
+                                                  both(y_pred, y).item()], dtype=np.float64)
+    np.savez_compressed(os.path.join(out_dir, 'losses_labels.npz'), **out)
+    print('wrote losses_labels.npz')
+
+
 def _sha(t: torch.Tensor) -> str:
     return hashlib.sha256(np.ascontiguousarray(t.numpy()).tobytes()).hexdigest()
 
@@ -194,6 +228,9 @@ CASES = [
     ('small_k70_n512_b2', helpers.small_k70_cfg, lambda: synthetic.make_batch('kitti', 2, 512, first_pair=29), 20, True),
     # a `transform` module (a SetAbstraction of its own) in front of the cloud features (deepclr.py:447,453-464)
     ('small_transform_n512_b2', helpers.small_transform_cfg, lambda: synthetic.make_batch('kitti', 2, 512, first_pair=31), 21, True),
+    # the other label types: 7 quaternion outputs (sigmoid / tanh on columns 3..6), 6 euler outputs (no activation)
+    ('small_quat_n512_b2', helpers.small_quat_cfg, lambda: synthetic.make_batch('kitti', 2, 512, first_pair=37), 22, True),
+    ('small_euler_n512_b2', helpers.small_euler_cfg, lambda: synthetic.make_batch('kitti', 2, 512, first_pair=41), 23, True),
 ]
 
 
@@ -218,9 +255,17 @@ def run_case(ref, name, cfg, x_np, wseed, full):
         err = (a - b).abs().max().item()
         assert a.shape == b.shape and err <= 1e-6 * max(1.0, a.abs().max().item()), (name, what, err)
 
-    mats_ref = np.stack([label_type.to_matrix(v.numpy().copy()) for v in y_ref])
-    mats_or = np.stack([olabels.dual_quat_to_matrix(v.numpy()) for v in y_or])
-    assert np.abs(mats_ref - mats_or).max() < 1e-6, name
+    # the reference's to_matrix of euler labels needs transforms3d.euler, which is not restated here: such a golden stores y
+    # without `mat`, and its tests convert both sides with deepclr_amd.labels
+    mats = {}
+    if cfg['label_type'] != 'POSE3D_EULER':
+        mats_ref = np.stack([label_type.to_matrix(v.numpy().copy()) for v in y_ref])
+        if cfg['label_type'] == 'POSE3D_DUAL_QUAT':
+            mats_or = np.stack([olabels.dual_quat_to_matrix(v.numpy()) for v in y_or])
+        else:
+            mats_or = np.stack([LabelType.create(cfg['label_type']).to_matrix(v.numpy()) for v in y_or])
+        assert np.abs(mats_ref - mats_or).max() < 1e-6, name
+        mats['mat'] = mats_ref
 
     # primitive-level records from the oracle (what the reference composition consumed); the sampling levels in order: those
     # of an optional `transform` module, then those of the cloud features
@@ -254,7 +299,7 @@ def run_case(ref, name, cfg, x_np, wseed, full):
         'x': x_np, 'weight_seed': np.int64(wseed), 'fps_idx': fps_idx.numpy().astype(np.int16),
         'bq_sha256': np.array([_sha(t) for t in bq]),
         'knn_sha256': np.array(_sha(knn_local)),
-        'y': y_ref.numpy(), 'mat': mats_ref, **extra,
+        'y': y_ref.numpy(), **mats, **extra,
     }
     if full:
         out.update(**{'bq%d' % i: t.numpy().astype(np.int16) for i, t in enumerate(bq)},
@@ -276,13 +321,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reference', default='/root/reference')
     ap.add_argument('--only-losses', action='store_true', help='regenerate losses.npz only')
-    ap.add_argument('--only', default=None, help='regenerate one case only')
+    ap.add_argument('--only', default=None, help="regenerate one case only ('losses_labels': that loss fixture)")
     args = ap.parse_args()
     torch.set_num_threads(8)
     ref = _load_reference(args.reference)
     if args.only is None:
         loss_golden(ref, HERE)
-    if args.only_losses:
+    if args.only in (None, 'losses_labels'):
+        label_loss_golden(ref, HERE)
+    if args.only_losses or args.only == 'losses_labels':
         return
     for name, cfg_fn, x_fn, wseed, full in CASES:
         if args.only is None or args.only == name:

@@ -29,6 +29,10 @@ GOLDEN_CASES = {
     # a `transform` module in front of the cloud features (reference deepclr.py:447,453-464; no shipped config has one):
     # 512 points -> 128 centroids x 64 features (module 0) -> 64 centroids x (32 + 32) features (module 1)
     'small_transform_n512_b2': ('small_transform', True),
+    # the other two label types of the reference (deepclr.py:275-281): 7 outputs with a sigmoid on column 3 and tanh on 4..6,
+    # and 6 outputs (translation + static-xyz euler angles in degrees) with no output activation
+    'small_quat_n512_b2': ('small_quat', True),
+    'small_euler_n512_b2': ('small_euler', True),
 }
 
 
@@ -105,6 +109,23 @@ def small_k70_cfg() -> dict:
     return cfg
 
 
+def small_quat_cfg() -> dict:
+    cfg = small_cfg()
+    cfg['label_type'] = 'POSE3D_QUAT'
+    return cfg
+
+
+def small_euler_cfg() -> dict:
+    cfg = small_cfg()
+    cfg['label_type'] = 'POSE3D_EULER'
+    return cfg
+
+
+def case_label_type(name: str):
+    from deepclr_amd.labels import LabelType
+    return LabelType.create(case_cfg(name)['label_type'])
+
+
 def custom_features_batch(n_pairs: int = 2, n_points: int = 384) -> np.ndarray:
     x = synthetic.make_batch('kitti', n_pairs, n_points, first_pair=21)
     extra = np.random.default_rng(33).uniform(-1.0, 1.0, size=x.shape[:2] + (2,)).astype(np.float32)
@@ -127,6 +148,10 @@ def case_cfg(name: str) -> dict:
         return small_two_level_cfg()
     if kind == 'small_transform':
         return small_transform_cfg()
+    if kind == 'small_quat':
+        return small_quat_cfg()
+    if kind == 'small_euler':
+        return small_euler_cfg()
     return small_cfg() if kind == 'small' else synthetic.model_cfg(kind)
 
 

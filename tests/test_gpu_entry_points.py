@@ -20,7 +20,7 @@ from deepclr_amd.config import model_config_from_dict
 from deepclr_amd.labels import LabelType
 from deepclr_amd.models import build_model, ModelInferenceHelper
 from deepclr_amd.pipeline import PipelinedForward, PipelinedSequence
-from helpers import GOLDEN_CASES, load_golden, small_cfg
+from helpers import GOLDEN_CASES, case_label_type, load_golden, small_cfg
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -53,12 +53,12 @@ def _models(cfg: dict, sd):
     return model.to(DEV).eval(), oracle.build_oracle_model(cfg, sd)
 
 
-def _mats(y) -> np.ndarray:
-    return np.stack([LabelType.POSE3D_DUAL_QUAT.to_matrix(v) for v in np.asarray(y, dtype=np.float64)])
+def _mats(y, lt=LabelType.POSE3D_DUAL_QUAT) -> np.ndarray:
+    return np.stack([lt.to_matrix(v) for v in np.asarray(y, dtype=np.float64)])
 
 
-def _mismatch(got, want_y, want_mat=None, exact=None):
-    """None if `got` (pairs, 8) matches want_y within RTOL / ATOL x scale, its 4x4 poses want_mat within POSE_ATOL and, where
+def _mismatch(got, want_y, want_mat=None, exact=None, lt=LabelType.POSE3D_DUAL_QUAT):
+    """None if `got` (pairs, lt.dim) matches want_y within RTOL / ATOL x scale, its 4x4 poses want_mat within POSE_ATOL and, where
     `exact` is given, equals it bit for bit; otherwise what differs."""
     if not torch.is_tensor(got):
         return 'returned {!r}'.format(type(got).__name__)
@@ -75,7 +75,7 @@ def _mismatch(got, want_y, want_mat=None, exact=None):
     if not torch.allclose(got, want_y, rtol=RTOL, atol=ATOL * scale):
         return 'outputs off by {:.3g} (scale {:.3g})'.format(err, scale)
     if got.shape[0]:
-        mat_err = float(np.abs(_mats(got.numpy()) - (_mats(want_y.numpy()) if want_mat is None else want_mat)).max())
+        mat_err = float(np.abs(_mats(got.numpy(), lt) - (_mats(want_y.numpy(), lt) if want_mat is None else want_mat)).max())
         if not mat_err < POSE_ATOL:
             return '4x4 pose off by {:.3g}'.format(mat_err)
     if exact is not None and not torch.equal(got, exact.detach().cpu()):
@@ -114,7 +114,10 @@ def test_pairwise_entry_points_on_every_golden(name):
     model, _ = _models(cfg, sd)
     x = torch.from_numpy(g['x']).to(DEV)
     b = x.shape[0] // 2
-    y_g, mat_g = g['y'], g['mat']
+    lt = case_label_type(name)
+    y_g = g['y']
+    assert y_g.shape == (b, lt.dim)
+    mat_g = g['mat'] if 'mat' in g.files else _mats(y_g, lt)     # euler goldens: no reference 4x4 (make_golden.py)
     with torch.no_grad():
         model(x.clone())                                          # the first, range-checked forward of the checkpoint
         want = model(x.clone())[0]
@@ -124,7 +127,7 @@ def test_pairwise_entry_points_on_every_golden(name):
     problems = []
 
     def check_all(got):
-        return _mismatch(got, y_g, mat_g, want if exact else None)
+        return _mismatch(got, y_g, mat_g, want if exact else None, lt)
 
     def row_api():
         return model.merge_rows(model.cloud_feature_rows(x, model.sample(x)), b)
@@ -150,7 +153,7 @@ def test_pairwise_entry_points_on_every_golden(name):
             if len(outs) != len(wants_y):
                 return '{} outputs for {} batches'.format(len(outs), len(wants_y))
             for i, (o, wy, we) in enumerate(zip(outs, wants_y, wants_exact)):
-                bad = _mismatch(o, wy, None, we if exact else None)
+                bad = _mismatch(o, wy, None, we if exact else None, lt)
                 if bad is not None:
                     return 'batch {}: {}'.format(i, bad)
             return None
@@ -168,7 +171,7 @@ def test_pairwise_entry_points_on_every_golden(name):
     helper = ModelInferenceHelper(model)
     for i in range(b):
         _judge(problems, name, 'predict[pair {}]'.format(i), lambda: helper.predict(x[b + i], x[i]).unsqueeze(0),
-               lambda got: _mismatch(got, y_g[[i]], mat_g[[i]], want_single[i] if exact else None))
+               lambda got: _mismatch(got, y_g[[i]], mat_g[[i]], want_single[i] if exact else None, lt))
     _judge(problems, name, 'predict_batch', lambda: helper.predict_batch(x[b:], x[:b]), check_all)
     model.check_range(synchronize=True)
     assert not problems, '\n'.join(problems)
@@ -194,6 +197,7 @@ def test_sequential_entry_points_on_every_golden(name):
     chunkings with chunks of 1 and 3 frames. Pose t = oracle(frame t-1 -> frame t), computed on this host."""
     g, cfg, sd = load_golden(name)
     model, orc = _models(cfg, sd)
+    lt = case_label_type(name)
     x_h = torch.from_numpy(g['x'])
     n_frames = x_h.shape[0]
     problems = []
@@ -204,7 +208,7 @@ def test_sequential_entry_points_on_every_golden(name):
         frames = frames_h.to(DEV)
         t = frames.shape[0]
         want = torch.cat([orc(torch.stack((frames_h[i - 1], frames_h[i]))) for i in range(1, t)]) if t > 1 \
-            else torch.zeros(0, 8)
+            else torch.zeros(0, lt.dim)
         tag = '{} frames'.format(t)
 
         def seq_predict():
@@ -213,9 +217,9 @@ def test_sequential_entry_points_on_every_golden(name):
             helper.finish()
             if outs[0] is not None:
                 raise AssertionError('first frame of a sequence returned a pose')
-            return torch.stack(outs[1:]) if t > 1 else torch.zeros(0, 8)
+            return torch.stack(outs[1:]) if t > 1 else torch.zeros(0, lt.dim)
 
-        _judge(problems, name, 'predict[{}]'.format(tag), seq_predict, lambda got: _mismatch(got, want))
+        _judge(problems, name, 'predict[{}]'.format(tag), seq_predict, lambda got: _mismatch(got, want, lt=lt))
         for lens in _chunkings(t):
             starts = np.cumsum([0] + lens)
             chunks = [frames[a:e] for a, e in zip(starts[:-1], starts[1:])]
@@ -225,7 +229,7 @@ def test_sequential_entry_points_on_every_golden(name):
                 return torch.cat([helper.predict_sequence(c) for c in chunks])
 
             _judge(problems, name, 'predict_sequence[{}, chunks {}]'.format(tag, lens), seq_chunks,
-                   lambda got: _mismatch(got, want))
+                   lambda got: _mismatch(got, want, lt=lt))
             for group, dense in ((1, False), (2, True), (3, True)):
                 def seq_runner():
                     runner = PipelinedSequence(model, depth=2, group=group, dense_group=dense)
@@ -236,7 +240,7 @@ def test_sequential_entry_points_on_every_golden(name):
                     return torch.cat(outs)
 
                 _judge(problems, name, 'PipelinedSequence[{}, chunks {}, group {}, dense_group {}]'.format(
-                    tag, lens, group, dense), seq_runner, lambda got: _mismatch(got, want))
+                    tag, lens, group, dense), seq_runner, lambda got: _mismatch(got, want, lt=lt))
     assert not problems, '\n'.join(problems)
 
 

@@ -17,7 +17,7 @@ from deepclr_amd import lib, ops, synthetic
 from deepclr_amd.config import model_config_from_dict
 from deepclr_amd.labels import LabelType
 from deepclr_amd.models import build_model, ModelInferenceHelper
-from helpers import GOLDEN_CASES, load_golden, case_cfg, degenerate_batch, pose_delta, small_cfg
+from helpers import GOLDEN_CASES, load_golden, case_cfg, case_label_type, degenerate_batch, pose_delta, small_cfg
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -30,8 +30,9 @@ def _models(cfg: dict, sd):
     return model.to(DEV).eval(), oracle.build_oracle_model(cfg, sd)
 
 
-def _mats(y):
-    return np.stack([LabelType.POSE3D_DUAL_QUAT.to_matrix(v) for v in y.detach().cpu().numpy()])
+def _mats(y, label_type=LabelType.POSE3D_DUAL_QUAT):
+    y = y.detach().cpu().numpy() if torch.is_tensor(y) else np.asarray(y)
+    return np.stack([label_type.to_matrix(v) for v in y.astype(np.float64)])
 
 
 PARITY_LOG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out', 'parity_errors.txt')
@@ -84,10 +85,15 @@ def test_model_matches_golden_and_oracle(name):
             assert tuple(t.shape) == tuple(g[key + '_shape'])
             got = t.contiguous().view(-1)[torch.from_numpy(g[key + '_pos']).to(DEV)]
             _close(got, g[key + '_val'], stage=name + ': ' + key + ' (sampled) vs reference golden')
-    _close(y, g['y'], stage=name + ': y (B, 8) vs reference golden')
+    lt = case_label_type(name)
+    assert tuple(y.shape) == tuple(g['y'].shape) == (x.shape[0] // 2, lt.dim)
+    _close(y, g['y'], stage=name + ': y (B, label_dim) vs reference golden')
     _close(y_feat, g['y'], stage=name + ': y via is_feat=True vs reference golden')
-    mat_err = float(np.abs(_mats(y) - g['mat']).max())
-    _close(torch.from_numpy(_mats(y)).float(), g['mat'].astype(np.float32), rtol=0, atol=1e-4, stage=name + ': 4x4 pose vs reference golden')
+    # the reference's 4x4 where the golden holds it; euler goldens hold none (its to_matrix needs a library absent where
+    # the goldens are made): their reference labels go through deepclr_amd.labels like the outputs
+    mat_g = g['mat'] if 'mat' in g.files else _mats(g['y'], lt)
+    mat_err = float(np.abs(_mats(y, lt) - mat_g).max())
+    _close(torch.from_numpy(_mats(y, lt)).float(), mat_g.astype(np.float32), rtol=0, atol=1e-4, stage=name + ': 4x4 pose vs reference golden')
     assert mat_err < 1e-4
     # and against the oracle recomputed on this host
     _close(y, orc(torch.from_numpy(g['x'])), stage=name + ': y vs oracle on this host')
@@ -1353,27 +1359,31 @@ def test_inference_script_call_sequence_runs_on_the_hip_path(tmp_path, sequentia
     assert stored['method']['name'] == 'DEEPCLR' and stored['method']['params']['weights_file'] == weights_file
 
 
-@pytest.mark.parametrize('cfg_name', ['small', 'custom_features'])
+@pytest.mark.parametrize('cfg_name', ['small', 'custom_features', 'small_quat', 'small_euler'])
 def test_training_step_gradients_match_the_oracle_autograd(cfg_name):
     """model.train() + forward(x, y=labels) + loss.backward() (the reference's training step, engine/engines.py:57-84):
     sampling / ball query / kNN on the HIP operators, gather and group through the HIP operators and their HIP backward,
     MLPs in torch. Loss value and EVERY parameter's gradient against torch autograd over the CPU oracle's functional
     restatement of the same network (float32 on both sides; the index operators are bit-exact, so both differentiate the
-    same piecewise-linear function)."""
-    from helpers import custom_features_batch, custom_features_cfg
-    if cfg_name == 'small':
-        cfg, x_np = small_cfg(), synthetic.make_batch('kitti', 2, 512, first_pair=41)
-    else:
+    same piecewise-linear function). small_quat / small_euler: the other label types, whose loss and gradients go through
+    the quaternion (sigmoid on column 3, tanh on 4..6) and the activation-free euler branches of the output layer."""
+    from helpers import custom_features_batch, custom_features_cfg, small_euler_cfg, small_quat_cfg
+    if cfg_name == 'custom_features':
         cfg, x_np = custom_features_cfg(), custom_features_batch()
+    else:
+        cfg = {'small': small_cfg, 'small_quat': small_quat_cfg, 'small_euler': small_euler_cfg}[cfg_name]()
+        x_np = synthetic.make_batch('kitti', 2, 512, first_pair=41)
     cfg['params']['loss'] = {'name': 'TransformLoss', 'params': {'p': 2, 'sx': 1.0, 'sq': 10.0}}
     sd = synthetic.random_state_dict(cfg, seed=23)
     model = build_model(model_config_from_dict(cfg))
     model.load_state_dict(sd, strict=False)
     model = model.to(DEV).train()
     x = torch.from_numpy(x_np)
-    labels = torch.from_numpy(np.stack([LabelType.POSE3D_DUAL_QUAT.from_matrix(synthetic.kitti_like_pair(41 + i, 16)[2])
+    lt = LabelType.create(cfg['label_type'])
+    labels = torch.from_numpy(np.stack([lt.from_matrix(synthetic.kitti_like_pair(41 + i, 16)[2])
                                         for i in range(2)]).astype(np.float32))
     y_pred, loss, _ = model(x.to(DEV), y=labels.to(DEV))
+    assert tuple(y_pred.shape) == (2, lt.dim)
     assert y_pred.requires_grad and loss.requires_grad
     loss.backward()
     # oracle: the same state_dict as leaf tensors, the same loss module on its outputs

@@ -354,6 +354,58 @@ def test_loss_values_match_reference_loss_modules():
         losses.transform_losses(y_pred * float('nan'), y, lt, 2)
 
 
+@pytest.mark.parametrize('label_type', ['POSE3D_EULER', 'POSE3D_QUAT', 'POSE3D_DUAL_QUAT'])
+def test_synthetic_weights_for_every_label_type(label_type):
+    """random_state_dict gives the output layer label_type.dim rows, loads strict into build_model and builds the oracle;
+    the output bias lies around LabelType.bias (none for euler labels); the other layers do not depend on the label type."""
+    import oracle
+    from deepclr_amd import synthetic
+    from deepclr_amd.config import model_config_from_dict
+    from deepclr_amd.models import build_model
+    from helpers import small_cfg
+    cfg = small_cfg()
+    cfg['label_type'] = label_type
+    lt = LabelType.create(label_type)
+    sd = synthetic.random_state_dict(cfg, seed=3)
+    assert tuple(sd['_merge_layers.1.output.weight'].shape) == (lt.dim, 256)
+    assert tuple(sd['_merge_layers.1.output.bias'].shape) == (lt.dim,)
+    model = build_model(model_config_from_dict(cfg))
+    model.load_state_dict(sd, strict=True)
+    assert model.label_dim == lt.dim
+    b = sd['_merge_layers.1.output.bias'].double().numpy()
+    centre = np.zeros(lt.dim) if lt.bias is None else np.array(lt.bias)
+    assert np.abs(b - centre).max() <= 0.05
+    dq = synthetic.random_state_dict(small_cfg(), seed=3)
+    for key, t in sd.items():
+        if not key.startswith('_merge_layers.1.output.'):
+            assert torch.equal(t, dq[key]), key
+    orc = oracle.build_oracle_model(cfg, sd)
+    x = torch.from_numpy(synthetic.make_batch('kitti', 1, 256))
+    y = orc(x)
+    assert tuple(y.shape) == (1, lt.dim) and bool(torch.isfinite(y).all())
+
+
+def test_loss_values_match_reference_loss_modules_at_other_label_types():
+    """tests/golden/losses_labels.npz: the reference's TransformLossCalculation / TransformLoss / TransformUncertaintyLoss /
+    AccumulatedLoss on random quaternion and euler labels (make_golden.py --only losses_labels)."""
+    from deepclr_amd.models.deepclr import AccumulatedLoss, TransformLoss, TransformUncertaintyLoss
+    from deepclr_amd import losses
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'losses_labels.npz'))
+    for name in ('POSE3D_QUAT', 'POSE3D_EULER'):
+        lt = LabelType.create(name)
+        y_pred, y = torch.from_numpy(g[name + '_y_pred']), torch.from_numpy(g[name + '_y'])
+        assert tuple(y.shape) == (8, lt.dim)
+        for p in (1, 2):
+            t, r = losses.transform_losses(y_pred, y, lt, p)
+            fixed = TransformLoss(lt, p=p, sx=1.5, sq=40.0)
+            learned = TransformUncertaintyLoss(lt, p=p, sx=0.3, sq=-2.5)
+            both = AccumulatedLoss([fixed, TransformLoss(lt, p=p, sx=0.5, sq=2.0)])
+            got = np.array([t.item(), r.item(), fixed(y_pred, y).item(), learned(y_pred, y).item(), both(y_pred, y).item()])
+            np.testing.assert_allclose(got, g['%s_p%d' % (name, p)], rtol=1e-6, err_msg='{} p={}'.format(name, p))
+        with pytest.raises(RuntimeError):
+            losses.transform_losses(y_pred * float('nan'), y, lt, 2)
+
+
 def test_no_kernel_spills():
     """The build records every kernel's registers / scratch (deepclr_amd/build.py): no kernel may use scratch memory --
     the 16384-point sampler once picked up 196 bytes of it from an innocent-looking epilogue and ran 20 % slower."""

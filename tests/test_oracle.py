@@ -9,7 +9,8 @@ import torch
 import oracle
 from oracle import labels as olabels
 from deepclr_amd import synthetic
-from helpers import GOLDEN_CASES, load_golden, sha, degenerate_batch
+from deepclr_amd.labels import LabelType
+from helpers import GOLDEN_CASES, case_label_type, load_golden, sha, degenerate_batch
 
 
 @pytest.mark.parametrize('name', list(GOLDEN_CASES))
@@ -42,8 +43,15 @@ def test_oracle_reproduces_golden(name):
             got = t.contiguous().view(-1)[torch.from_numpy(g[key + '_pos'])].numpy()
             np.testing.assert_allclose(got, g[key + '_val'], rtol=1e-4, atol=1e-5)
     np.testing.assert_allclose(y.numpy(), g['y'], rtol=1e-4, atol=1e-5)
-    mats = np.stack([olabels.dual_quat_to_matrix(v) for v in y.numpy()])
-    assert np.abs(mats - g['mat']).max() < 1e-4
+    lt = case_label_type(name)
+    if lt == LabelType.POSE3D_DUAL_QUAT:
+        mats = np.stack([olabels.dual_quat_to_matrix(v) for v in y.numpy()])
+        assert np.abs(mats - g['mat']).max() < 1e-4
+    elif 'mat' in g.files:                          # quaternion labels: the reference's 4x4
+        mats = np.stack([lt.to_matrix(v) for v in y.numpy()])
+        assert np.abs(mats - g['mat']).max() < 1e-4
+    else:                                           # euler labels: no reference 4x4 in the golden (make_golden.py)
+        assert lt == LabelType.POSE3D_EULER
 
 
 def _fps_reference_cases(golden_dir):
