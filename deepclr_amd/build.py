@@ -1,5 +1,6 @@
-"""Build libdeepclr_amd.so (inference ABI, include/deepclr_amd.h) and libdeepclr_amd_train.so (training kernels,
-include/deepclr_amd_train.h) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libdeepclr_amd.so (inference ABI, include/deepclr_amd.h), libdeepclr_amd_train.so (set-abstraction training
+kernels, include/deepclr_amd_train.h) and libdeepclr_amd_flow_train.so (flow-embedding training kernels,
+include/deepclr_amd_flow_train.h) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 Every object is compiled with -Rpass-analysis=kernel-resource-usage; the remarks are condensed into
 csrc/<name>.usage.txt (kernel, VGPRs, scratch bytes, occupancy, LDS bytes). kernel_usage() reads them:
@@ -17,6 +18,9 @@ HEADERS = ['common.h', 'mma.h', 'mma16f.h', os.path.join('..', '..', 'include', 
 TRAIN_LIB = os.path.join(CSRC, 'libdeepclr_amd_train.so')
 TRAIN_SOURCES = ['sa_train.hip']
 TRAIN_HEADERS = HEADERS + [os.path.join('..', '..', 'include', 'deepclr_amd_train.h')]
+FLOW_TRAIN_LIB = os.path.join(CSRC, 'libdeepclr_amd_flow_train.so')
+FLOW_TRAIN_SOURCES = ['flow_train.hip']
+FLOW_TRAIN_HEADERS = HEADERS + [os.path.join('..', '..', 'include', 'deepclr_amd_flow_train.h')]
 # -ffp-contract=off: the distance recipe shared with the oracle is one rounding per operation;
 # MLP code requests FMA explicitly.
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall',
@@ -87,11 +91,17 @@ def train_kernel_usage() -> dict:
     return _usage(TRAIN_SOURCES)
 
 
+def flow_train_kernel_usage() -> dict:
+    """kernel_usage() of libdeepclr_amd_flow_train.so."""
+    return _usage(FLOW_TRAIN_SOURCES)
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Both libraries; returns the path of libdeepclr_amd.so."""
+    """All three libraries; returns the path of libdeepclr_amd.so."""
     hipcc = _hipcc()
     jobs, links = [], []
-    for lib, sources, header_names in ((LIB, SOURCES, HEADERS), (TRAIN_LIB, TRAIN_SOURCES, TRAIN_HEADERS)):
+    for lib, sources, header_names in ((LIB, SOURCES, HEADERS), (TRAIN_LIB, TRAIN_SOURCES, TRAIN_HEADERS),
+                                       (FLOW_TRAIN_LIB, FLOW_TRAIN_SOURCES, FLOW_TRAIN_HEADERS)):
         headers = [os.path.join(CSRC, h) for h in header_names]
         objs, lib_jobs = [], []
         for src in sources:

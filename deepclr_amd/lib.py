@@ -70,6 +70,16 @@ TRAIN_SIGNATURES = {
 }
 TRAIN_LIB_PATH = os.path.join(_CSRC, 'libdeepclr_amd_train.so')
 
+# name -> argtypes; every entry point declared in include/deepclr_amd_flow_train.h (libdeepclr_amd_flow_train.so)
+FLOW_TRAIN_SIGNATURES = {
+    'dclr_flow_train_version': [],
+    'dclr_flow_train_forward': [_i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    'dclr_flow_train_workspace_bytes': [_i, _i, _i, _i],
+    'dclr_flow_train_backward': [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p,
+                                 ctypes.c_longlong, _p],
+}
+FLOW_TRAIN_LIB_PATH = os.path.join(_CSRC, 'libdeepclr_amd_flow_train.so')
+
 MERGE_MAX_LAYERS, MERGE_MAX_FC = 8, 4
 MERGE_EVENTS = 6 + MERGE_MAX_FC
 
@@ -159,6 +169,27 @@ def load_train() -> ctypes.CDLL:
             fn.restype = ctypes.c_longlong if name == 'dclr_sa_msg_train_workspace_bytes' else _i
         _train_lib = lib
     return _train_lib
+
+
+_flow_train_lib: Optional[ctypes.CDLL] = None
+
+
+def load_flow_train() -> ctypes.CDLL:
+    """Load the flow-embedding training library (forward with argmax, backward of the weights and both clouds); raises if
+    it has not been built."""
+    global _flow_train_lib
+    if _flow_train_lib is None:
+        if not os.path.exists(FLOW_TRAIN_LIB_PATH):
+            raise RuntimeError(
+                "deepclr_amd: {} is missing. Build it with `python -m deepclr_amd.build` "
+                "(hipcc --offload-arch=gfx950); there is no CPU fallback.".format(FLOW_TRAIN_LIB_PATH))
+        lib = ctypes.CDLL(FLOW_TRAIN_LIB_PATH)
+        for name, argtypes in FLOW_TRAIN_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = ctypes.c_longlong if name == 'dclr_flow_train_workspace_bytes' else _i
+        _flow_train_lib = lib
+    return _flow_train_lib
 
 
 def check(code: int, what: str) -> None:

@@ -147,6 +147,42 @@ class SetAbstraction(DeepCLRModule):
 # --------------------------------------------------------------------------------------------------
 # flow embedding
 # --------------------------------------------------------------------------------------------------
+class FlowTrainFunction(torch.autograd.Function):
+    """The fused flow embedding with a backward (csrc/flow_train.hip): inputs the template / source clouds (B, 67, P0),
+    (B, 67, P1), the kNN slots idx (B, P0, k) int32, the radius, then the conv weights and biases W1 b1 W2 b2 W3 b3 ->
+    cat(xyz0, max over the slots) (B, 259, P0), as MotionEmbeddingBase.forward_train. Saves the pooled features, each
+    channel's argmax slot and the layer-1 feature products; backward rebuilds the rest and returns the gradients of the
+    weights and, where autograd asks for them, of both clouds."""
+
+    @staticmethod
+    def forward(ctx, clouds0, clouds1, idx, radius, *params):
+        weights = ops.pack_flow_train_mlp(params)                  # per call: optimizer steps update params in place
+        c0 = clouds0.detach().transpose(1, 2).contiguous()
+        c1 = clouds1.detach().transpose(1, 2).contiguous()
+        pooled, arg, pt, ps = ops.flow_train_forward(c0, c1, idx, weights, radius)
+        ctx.save_for_backward(c0, c1, idx, weights, pt, ps, pooled, arg)
+        ctx.shapes = [p.shape for p in params]
+        return torch.cat((clouds0[:, :3, :].detach(), pooled), dim=1)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        c0, c1, idx, weights, pt, ps, pooled, arg = ctx.saved_tensors
+        need0, need1 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        grad, g0, g1 = ops.flow_train_backward(grad_out[:, 3:, :].contiguous(), c0, c1, idx, weights, pt, ps, pooled,
+                                               arg, input_grads=need0 or need1)
+        d0 = d1 = None
+        if need0:
+            d0 = g0.transpose(1, 2).contiguous()
+            d0[:, :3, :] += grad_out[:, :3, :]
+        if need1:
+            d1 = g1.transpose(1, 2).contiguous()
+        grads, offset = [], 0
+        for shape in ctx.shapes:
+            grads.append(grad.narrow(0, offset, shape.numel()).view(shape))
+            offset += shape.numel()
+        return (d0, d1, None, None, *grads)
+
+
 class MotionEmbeddingBase(nn.Module):
     """kNN grouping (or, with k == 0, GlobalGrouping: every point of the pair's source cloud, reference
     deepclr.py:108-139,186-187) + shared MLP + radius mask + max (reference: deepclr.py:176-231)."""
@@ -170,9 +206,50 @@ class MotionEmbeddingBase(nn.Module):
         self._conv = Conv1dMultiLayer([c_in, *mlp], batch_norm=batch_norm)
         self._cache = PackedCache()
         self._cache_composed = PackedCache()
+        self._fused_shape = (self._feat_dim == ops.FLOW_TRAIN_FEAT and append_features and list(mlp) == [128, 128, 256]
+                             and 1 <= k <= 32 and not batch_norm)
+        self.fused_training = False              # True: forward_train takes the fused training kernels (csrc/flow_train.hip)
+                                                 # where fused_training_applies(); DeepCLR.set_fused_training(merge=True)
 
     def output_dim(self) -> int:
         return self._point_dim + self._conv.output_dim()
+
+    def fused_training_shape(self) -> bool:
+        """The shape the fused training kernels take: 3 + 64 + 64 inputs, append_features, mlp [128, 128, 256],
+        1 <= k <= 32, no batch norm."""
+        return self._fused_shape
+
+    def fused_training_applies(self, clouds0: Optional[torch.Tensor] = None, clouds1: Optional[torch.Tensor] = None) -> bool:
+        """forward_train takes _forward_fused_train: the flag is set, the shape is the fused kernels', the module is in
+        training mode with gradients enabled, and the clouds (if given) have 67 channels."""
+        shaped = all(c is None or (c.dim() == 3 and c.shape[1] == self._point_dim + ops.FLOW_TRAIN_FEAT)
+                     for c in (clouds0, clouds1))
+        return (self.fused_training and self._fused_shape and self.training and torch.is_grad_enabled()
+                and not self._conv.has_dropout() and shaped)
+
+    def _knn_slots(self, clouds0: torch.Tensor, clouds1: torch.Tensor) -> torch.Tensor:
+        """(B, P0, k) int32 source points of every template point's k nearest neighbours (dclr_knn); raises where a template
+        point has fewer than k."""
+        b, _, p0 = clouds0.shape
+        p1 = clouds1.shape[2]
+        d, k = self._point_dim, self._k
+        dev = clouds0.device
+        xyz0 = clouds0[:, :d, :].detach().transpose(1, 2).contiguous()
+        xyz1 = clouds1[:, :d, :].detach().transpose(1, 2).contiguous()
+        row = torch.empty(b * p0 * k, dtype=torch.int64, device=dev)
+        col = torch.empty(b * p0 * k, dtype=torch.int64, device=dev)
+        ops._call('dclr_knn', 'knn', b, p1, p0, k, xyz1.data_ptr(), xyz0.data_ptr(), row.data_ptr(), col.data_ptr(),
+                  lib.stream_ptr())
+        if bool((col < 0).any()):
+            raise RuntimeError("kNN grouping: a template point has fewer than k = {} source points".format(k))
+        return (col.view(b, p0, k) - (torch.arange(b, device=dev) * p1).view(b, 1, 1)).to(torch.int32).contiguous()
+
+    def _forward_fused_train(self, clouds0: torch.Tensor, clouds1: torch.Tensor) -> torch.Tensor:
+        """forward_train on the fused training kernels: the same neighbour lists, output and gradients, with O(points)
+        saved state instead of every activation of every (point, neighbour) row."""
+        clouds0, clouds1 = clouds0.contiguous(), clouds1.contiguous()
+        idx = self._knn_slots(clouds0, clouds1)
+        return FlowTrainFunction.apply(clouds0, clouds1, idx, self._radius, *self._conv.parameters())
 
     def _packed(self):
         def build():
@@ -247,22 +324,17 @@ class MotionEmbeddingBase(nn.Module):
         """forward() with a gradient (reference: deepclr.py:201-231 under autograd): the neighbour lists come from the HIP
         search (indices: nothing to differentiate), the source rows are gathered through GroupingOperation -- dclr_group_points
         forward, dclr_group_points_grad backward, what the reference's `pts1[group_index]` gets from torch's index kernels --
-        and the shared MLP, the radius mask and the max run in torch, whose autograd has their backward."""
+        and the shared MLP, the radius mask and the max run in torch, whose autograd has their backward. With fused_training set
+        (DeepCLR.set_fused_training(merge=True)) and the fused shape, _forward_fused_train runs instead."""
+        if self.fused_training_applies(clouds0, clouds1):
+            return self._forward_fused_train(clouds0, clouds1)
         b, c, p0 = clouds0.shape
         p1 = clouds1.shape[2]
         d, k = self._point_dim, self._k
         dev = clouds0.device
         clouds0, clouds1 = clouds0.contiguous(), clouds1.contiguous()
         if k > 0:
-            xyz0 = clouds0[:, :d, :].detach().transpose(1, 2).contiguous()
-            xyz1 = clouds1[:, :d, :].detach().transpose(1, 2).contiguous()
-            row = torch.empty(b * p0 * k, dtype=torch.int64, device=dev)
-            col = torch.empty(b * p0 * k, dtype=torch.int64, device=dev)
-            ops._call('dclr_knn', 'knn', b, p1, p0, k, xyz1.data_ptr(), xyz0.data_ptr(), row.data_ptr(), col.data_ptr(),
-                      lib.stream_ptr())
-            if bool((col < 0).any()):
-                raise RuntimeError("kNN grouping: a template point has fewer than k = {} source points".format(k))
-            idx = (col.view(b, p0, k) - (torch.arange(b, device=dev) * p1).view(b, 1, 1)).to(torch.int32).contiguous()
+            idx = self._knn_slots(clouds0, clouds1)
         else:
             k = p1
             idx = torch.arange(p1, dtype=torch.int32, device=dev).view(1, 1, p1).expand(b, p0, p1).contiguous()
@@ -871,13 +943,15 @@ class DeepCLR(BaseModel):
                 if callable(fn) and mod is not self:
                     fn()
 
-    def set_fused_training(self, enabled: bool = True) -> List[str]:
+    def set_fused_training(self, enabled: bool = True, merge: bool = False) -> List[str]:
         """Let a training forward (model.train(), gradients on) run the set-abstraction levels on the fused training
         kernels (csrc/sa_train.hip) instead of composing them in torch: sets PointnetSAModuleMSG.fused_training on every
         level. A level takes the fused path only with the fused kernel's shape, no batch norm and an input without
         gradient -- the first level of the first per-cloud module; a second level or a module behind a `transform`
         reads features that carry a gradient and stays composed. Returns the names of the levels that will run fused
-        (none with enabled=False)."""
+        (none with enabled=False). With merge=True the flow embedding's flag (MotionEmbeddingBase.fused_training) is set as
+        well, and '_merge_layers.0' is listed when its shape is the fused kernels' (csrc/flow_train.hip: 64 features per
+        cloud, append_features, mlp [128, 128, 256], 1 <= k <= 32, no batch norm); merge=False leaves it off."""
         fused, grad_in = [], False
         for i, layer in enumerate(self._cloud_layers):
             for name in ('_sa0', '_sa1'):
@@ -888,6 +962,11 @@ class DeepCLR(BaseModel):
                 if enabled and level.fused and not level._bn and not grad_in:
                     fused.append('_cloud_layers.{}.{}'.format(i, name))
                 grad_in = grad_in or any(p.requires_grad for p in level.parameters())
+        embedding = getattr(self._merge_layers[0], '_embedding', None)
+        if isinstance(embedding, MotionEmbeddingBase):
+            embedding.fused_training = bool(enabled and merge)
+            if embedding.fused_training and embedding.fused_training_shape():
+                fused.append('_merge_layers.0')
         return fused
 
     # -- row-level pipeline (what bench.py and the sharded runner drive) ---------------------------

@@ -681,3 +681,97 @@ def sa_msg_train_backward(grad_out: torch.Tensor, arg: torch.Tensor, xyz: torch.
                 lib.ptr(feats), new_xyz.data_ptr(), weights.data_ptr(), grad_out.data_ptr(), arg.data_ptr(),
                 grad.data_ptr(), ws.data_ptr(), nbytes, lib.stream_ptr())
     return grad
+
+
+# ------------------------------------------------------------------------------------------------
+# training: the fused flow embedding's forward with argmax and its backward (libdeepclr_amd_flow_train.so)
+# ------------------------------------------------------------------------------------------------
+FLOW_TRAIN_GRAD_FLOATS = 66432      # W1 (128 x 131) b1 W2 (128 x 128) b2 W3 (256 x 128) b3 (include/deepclr_amd_flow_train.h)
+FLOW_TRAIN_MLP_FLOATS = 101248      # ... then W2^T (128 x 128) and W1^T padded to (144 x 128)
+FLOW_TRAIN_FEAT = 64
+
+
+def _call_flow_train(name: str, what: str, *args) -> None:
+    lib.check(getattr(lib.load_flow_train(), name)(*args), what)
+
+
+def pack_flow_train_mlp(params: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Conv weights / biases [W1 b1 W2 b2 W3 b3] of the flow embedding's 131 -> 128 -> 128 -> 256 MLP (W (out, in, 1))
+    -> the flat buffer of dclr_flow_train_*. Built from the tensors as they are at the call (an optimizer step updates
+    them in place), without gradient (FlowTrainFunction has the backward)."""
+    w1, b1, w2, b2, w3, b3 = (t.detach().to(torch.float32) for t in params)
+    w1, w2, w3 = w1.reshape(128, 131), w2.reshape(128, 128), w3.reshape(256, 128)
+    w1t = torch.cat((w1.t(), w1.new_zeros(144 - 131, 128)), dim=0)
+    return torch.cat([t.reshape(-1) for t in (w1, b1, w2, b2, w3, b3, w2.t().contiguous(), w1t.contiguous())]).contiguous()
+
+
+def _flow_clouds(cloud0: torch.Tensor, cloud1: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    for name, t in (('cloud0', cloud0), ('cloud1', cloud1)):
+        lib.dev_f32(t, name)
+        if t.dim() != 3 or t.shape[2] != 3 + FLOW_TRAIN_FEAT:
+            raise RuntimeError("{}: (pairs, n, 67) point-major rows [xyz | 64 features] expected, got {}".format(
+                name, tuple(t.shape)))
+    if cloud0.shape[0] != cloud1.shape[0]:
+        raise RuntimeError("cloud0 / cloud1: the same number of pairs")
+    return cloud0, cloud1
+
+
+def flow_train_forward(cloud0: torch.Tensor, cloud1: torch.Tensor, idx: torch.Tensor, weights: torch.Tensor,
+                       radius: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """cloud0 (B, P0, 67), cloud1 (B, P1, 67) point-major, idx (B, P0, k) int32 source points, weights from
+    pack_flow_train_mlp -> pooled (B, 256, P0), arg (B, 256, P0) int32 (first slot reaching each maximum), pt (B, P0, 128)
+    and ps (B, P1, 128) (the layer-1 feature products the backward reuses)."""
+    cloud0, cloud1 = _flow_clouds(cloud0, cloud1)
+    weights = lib.dev_f32(weights, 'weights')
+    b, n0, _ = cloud0.shape
+    n1 = cloud1.shape[1]
+    if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 3
+            and tuple(idx.shape[:2]) == (b, n0)):
+        raise RuntimeError("idx: (B, P0, k) int32 contiguous GPU tensor")
+    if weights.numel() != FLOW_TRAIN_MLP_FLOATS:
+        raise RuntimeError("weights: {} floats expected (pack_flow_train_mlp)".format(FLOW_TRAIN_MLP_FLOATS))
+    k = idx.shape[2]
+    dev = cloud0.device
+    pt = torch.empty(b, n0, 128, dtype=torch.float32, device=dev)
+    ps = torch.empty(b, n1, 128, dtype=torch.float32, device=dev)
+    pooled = torch.empty(b, 256, n0, dtype=torch.float32, device=dev)
+    arg = torch.empty(b, 256, n0, dtype=torch.int32, device=dev)
+    _call_flow_train('dclr_flow_train_forward', 'flow_train_forward', b, n0, n1, k, FLOW_TRAIN_FEAT, float(radius),
+                     cloud0.data_ptr(), cloud1.data_ptr(), idx.data_ptr(), weights.data_ptr(), pt.data_ptr(),
+                     ps.data_ptr(), pooled.data_ptr(), arg.data_ptr(), lib.stream_ptr())
+    return pooled, arg, pt, ps
+
+
+def flow_train_workspace_bytes(pairs: int, n0: int, n1: int, k: int) -> int:
+    nbytes = lib.load_flow_train().dclr_flow_train_workspace_bytes(pairs, n0, n1, k)
+    lib.check(nbytes if nbytes < 0 else 0, 'flow_train_workspace_bytes')
+    return nbytes
+
+
+def flow_train_backward(grad_pooled: torch.Tensor, cloud0: torch.Tensor, cloud1: torch.Tensor, idx: torch.Tensor,
+                        weights: torch.Tensor, pt: torch.Tensor, ps: torch.Tensor, pooled: torch.Tensor,
+                        arg: torch.Tensor, input_grads: bool = True
+                        ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """grad_pooled (B, 256, P0) and the outputs of flow_train_forward on the same inputs -> the gradient of the first
+    FLOW_TRAIN_GRAD_FLOATS floats of `weights` and, with input_grads, of cloud0 / cloud1 (point-major, like them; cloud0's
+    xyz columns without the gradient of the xyz rows the caller copies into its output). Bit-identical from run to run."""
+    cloud0, cloud1 = _flow_clouds(cloud0, cloud1)
+    grad_pooled = lib.dev_f32(grad_pooled, 'grad_pooled')
+    b, n0, _ = cloud0.shape
+    n1, k = cloud1.shape[1], idx.shape[2]
+    for name, t in (('pooled', pooled), ('arg', arg), ('grad_pooled', grad_pooled)):
+        if tuple(t.shape) != (b, 256, n0) or not t.is_contiguous():
+            raise RuntimeError("{}: (B, 256, P0) contiguous expected".format(name))
+    if tuple(pt.shape) != (b, n0, 128) or tuple(ps.shape) != (b, n1, 128) or arg.dtype != torch.int32:
+        raise RuntimeError("pt / ps / arg: the outputs of flow_train_forward on the same clouds")
+    dev = cloud0.device
+    nbytes = flow_train_workspace_bytes(b, n0, n1, k)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    grad = torch.empty(FLOW_TRAIN_GRAD_FLOATS, dtype=torch.float32, device=dev)
+    g0 = torch.empty(b, n0, 67, dtype=torch.float32, device=dev) if input_grads else None
+    g1 = torch.empty(b, n1, 67, dtype=torch.float32, device=dev) if input_grads else None
+    _call_flow_train('dclr_flow_train_backward', 'flow_train_backward', b, n0, n1, k, FLOW_TRAIN_FEAT,
+                     cloud0.data_ptr(), cloud1.data_ptr(), idx.data_ptr(), weights.data_ptr(), pt.data_ptr(),
+                     ps.data_ptr(), pooled.data_ptr(), arg.data_ptr(), grad_pooled.data_ptr(), grad.data_ptr(),
+                     int(bool(input_grads)), lib.ptr(g0), lib.ptr(g1), ws.data_ptr(), nbytes, lib.stream_ptr())
+    return grad, g0, g1

@@ -1,5 +1,6 @@
-"""One training step (forward + loss + backward + SGD step) with the set abstraction composed in torch and with the fused
-training kernels (DeepCLR.set_fused_training): median ms per step and torch.cuda.max_memory_allocated.
+"""One training step (forward + loss + backward + SGD step) composed in torch, with the set abstraction on the fused training
+kernels (DeepCLR.set_fused_training) and with the set abstraction and the flow embedding fused (merge=True): median ms
+per step and torch.cuda.max_memory_allocated.
 
     python profiles/train_step.py --workload kitti16k [--steps 10 --warmup 3] [--json out.json]
 
@@ -26,14 +27,14 @@ WORKLOADS = {'kitti16k': ('kitti', 16384), 'kitti64k': ('kitti', 65536), 'modeln
 PAIRS = 5
 
 
-def run(workload: str, fused: bool, steps: int, warmup: int) -> dict:
+def run(workload: str, mode: str, steps: int, warmup: int) -> dict:
     kind, n = WORKLOADS[workload]
     cfg = synthetic.model_cfg(kind)
     cfg['params']['loss'] = {'name': 'TransformLoss', 'params': {'p': 2, 'sx': 1.0, 'sq': 10.0}}
     model = build_model(model_config_from_dict(cfg))
     model.load_state_dict(synthetic.random_state_dict(cfg, seed=0), strict=False)
     model = model.to('cuda:0').train()
-    levels = model.set_fused_training(fused)
+    levels = model.set_fused_training(mode != 'composed', merge=mode == 'sa+flow fused')
     x = torch.from_numpy(synthetic.make_batch(kind, PAIRS, n)).to('cuda:0')
     y = torch.from_numpy(np.stack([LabelType.POSE3D_DUAL_QUAT.from_matrix(synthetic.kitti_like_pair(i, 16)[2])
                                    for i in range(PAIRS)]).astype(np.float32)).to('cuda:0')
@@ -51,7 +52,7 @@ def run(workload: str, fused: bool, steps: int, warmup: int) -> dict:
         torch.cuda.synchronize()
         if i >= warmup:
             times.append(1e3 * (time.perf_counter() - t0))
-    return {'workload': workload, 'sa': 'fused' if fused else 'composed', 'fused_levels': levels,
+    return {'workload': workload, 'sa': mode, 'fused_levels': levels,
             'median_ms': statistics.median(times), 'min_ms': min(times), 'steps': steps,
             'max_memory_allocated_mb': torch.cuda.max_memory_allocated() / 2 ** 20, 'loss': float(loss.detach())}
 
@@ -61,13 +62,13 @@ def main() -> None:
     ap.add_argument('--workload', choices=sorted(WORKLOADS), required=True)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--json', default=None, help='append the two result lines to this file')
+    ap.add_argument('--json', default=None, help='append the three result lines to this file')
     args = ap.parse_args()
     rows = []
-    for fused in (False, True):
+    for mode in ('composed', 'fused', 'sa+flow fused'):
         torch.cuda.empty_cache()
-        rows.append(run(args.workload, fused, args.steps, args.warmup))
-        print('%-9s %-8s median %9.2f ms/step  peak %9.1f MB  loss %.6f' % (
+        rows.append(run(args.workload, mode, args.steps, args.warmup))
+        print('%-9s %-13s median %9.2f ms/step  peak %9.1f MB  loss %.6f' % (
             rows[-1]['workload'], rows[-1]['sa'], rows[-1]['median_ms'], rows[-1]['max_memory_allocated_mb'], rows[-1]['loss']),
             flush=True)
     if args.json:
